@@ -42,7 +42,18 @@ quota more processes only time-share the same cores); its bitstreams double
 as a parity spot check of the timed GPU output.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--channels C]
-                  [--total-channels T]
+                  [--dump-outputs DIR] [--full [--total-channels T] ...]
+A plain run does what the headline needs and no more: the input of the W + K
+superframes, an untimed serialised pass over them (kernels loaded, the device
+under load as under --full), W pipelined warm-up steps, the K timed pipelined steps, and the result line with the
+headline fields (metric, value, unit, ms_per_step, step, config).  Everything
+else described above -- the serialised step and the roofline, the strong-
+scaling leg, decode, TX front end, round trip, host-fed, duplex, crypt, VAD
+and modem legs, the bitstream gather, the CPU baseline and its parity spot
+check -- runs under --full, which adds its fields to the same line.
+--dump-outputs DIR writes what the last timed step produced (bits and a
+seeded sample of the in-place NPP output) as DIR/<name>.npy; the input is
+seeded, so two builds can be compared array for array.
 With --gpus N > 1 and no WORLD_SIZE in the environment, bench.py starts the N
 rank processes itself (before touching the GPU); under torch.distributed.run
 it is one of them.
@@ -88,6 +99,14 @@ def parse(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the serialised step and its roofline, the decode, "
+                         "host-fed, duplex, crypt, VAD, modem, strong-scaling, round-trip and TX "
+                         "legs, the bitstream gather and the CPU baseline with its parity check "
+                         "(the options below choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step produced to "
+                         "DIR/<name>.npy (rank 0's channels)")
     ap.add_argument("--channels", type=int, default=262144, help="channels per GPU (weak)")
     ap.add_argument("--total-channels", type=int, default=262144,
                     help="config 4 strong-scaling leg: channels split across the ranks "
@@ -447,6 +466,35 @@ def pipe_leg(rig, wl, K, W):
     return rig.max_over_ranks(dt), ems
 
 
+DUMP_ALL_BITS_MAX = 262144    # channels whose bits are written whole (11.5 MB as float32)
+DUMP_PCM_CHANNELS = 16384     # sampled channels of NPP output written (35.4 MB as float32)
+
+
+def dump_outputs(wl, s, out_dir):
+    """--dump-outputs: what the caller of the timed path holds after timed
+    superframe s, as float32 .npy files of under 64 MB in all: bits.npy (the
+    11 bitstream bytes of every channel, [C, 11]; of the sampled channels
+    beyond 262,144), npp_pcm.npy (the NPP output melpe_a left in place of the
+    PCM, [n, 540], of n = min(C, 16,384) channels sampled with a fixed seed)
+    and channels.npy (the sampled channels' indices within this rank's
+    shard).  The input is the seeded synthetic signal, so two runs with the
+    same arguments write the same arrays."""
+    C = wl.bits.shape[1]
+    n = min(C, DUMP_PCM_CHANNELS)
+    chans = np.sort(np.random.default_rng(RUN_SEED).choice(C, size=n, replace=False))
+    bits = wl.bits[s].cpu().numpy()
+    if C > DUMP_ALL_BITS_MAX:
+        bits = bits[chans]
+    idx = wl.rig.torch.from_numpy(chans).to(wl.pcm.device)
+    pcm = wl.pcm[s].index_select(0, idx).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "bits.npy"), bits.astype(np.float32))
+    np.save(os.path.join(out_dir, "npp_pcm.npy"), pcm.astype(np.float32))
+    np.save(os.path.join(out_dir, "channels.npy"), chans.astype(np.float64))
+    log("outputs of superframe %d written to %s (bits of %d channels, NPP output of %d)"
+        % (s, out_dir, bits.shape[0], n))
+
+
 def host_leg(rig, C, first, K, W, dev_bits, world):
     """The host-fed form of the headline (melpe/melpe.c:91-99's contract:
     the caller hands host buffers): the same channels and synthetic input,
@@ -771,21 +819,53 @@ def run(args, rank, world, local, backend="nccl", rig_cls=None, workload_cls=Non
     wl = Workload(rig, C, rank * C, W + K)
     log("rank %d: %d channels x %d superframes of input resident" % (rank, C, W + K))
     # one step = melpe_a on every channel = k_enc_npp then k_enc_ana
-    # the serialised step: each launch alone, HIP events around each (the
-    # kernels' own durations, for the roofline)
-    ser_s, (npp_kms, ana_kms) = encode_leg(rig, wl, K, W)
-    enc_kms = npp_kms + ana_kms
-    log("encode, serialised: %.1f ms/step (k_enc_npp %.1f ms + k_enc_ana %.1f ms)"
-        % (1e3 * ser_s / K, npp_kms, ana_kms))
-    # the headline step: the same work pipelined, from fresh state on the
-    # same input; its bits must equal the serialised run's
-    ser_bits = wl.bits.clone()
+    if args.full:
+        # the serialised step: each launch alone, HIP events around each (the
+        # kernels' own durations, for the roofline)
+        ser_s, (npp_kms, ana_kms) = encode_leg(rig, wl, K, W)
+        enc_kms = npp_kms + ana_kms
+        log("encode, serialised: %.1f ms/step (k_enc_npp %.1f ms + k_enc_ana %.1f ms)"
+            % (1e3 * ser_s / K, npp_kms, ana_kms))
+        ser_bits = wl.bits.clone()
+    else:
+        # the same W + K serialised steps untimed, without events, copies or
+        # comparison: the headline is taken as under --full, on a device
+        # that has been under load for the serialised leg's W + K steps, so
+        # that the two forms read the same (alternating runs at 88 timed
+        # steps: 34.11-34.13 ms plain, 34.14 ms under --full)
+        for s in range(W + K):
+            wl.npp(s)
+            wl.ana(s)
+        rig.sync()
+    # the headline step: the work pipelined, from fresh state on the same
+    # input (under --full its bits must equal the serialised run's)
     wl.restart()
     enc_s, pipe_ems = pipe_leg(rig, wl, K, W)
+    log("encode, pipelined: %.1f ms/step" % (1e3 * enc_s / K))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, W + K - 1, args.dump_outputs)
+    value = world * C * K * SF_SECONDS / enc_s
+    line = {
+        "metric": "MELPe-1200 channel-seconds encoded/sec (node)",
+        "value": value, "unit": "channel-s/s", "n_gpus": world, "steps": K, "warmup": W,
+        "ms_per_step": 1e3 * enc_s / K, "higher_is_better": True, "scaling": "weak",
+        "step": {"form": "pipelined: superframe k's analysis beside superframe k+1's NPP "
+                         "(melpe_encode_pipe_dev); the timed region holds K NPPs and K analyses",
+                 "ms_per_step_events": pipe_ems},
+        "vs_baseline": None, "dtype": "int16/int32 saturating fixed point",
+        "data": "synthetic (integer speech-like generator csrc/synth.h, run seed %d)" % RUN_SEED,
+        "config": {"workload": "config 4: %d channels per GPU, melpe_a per superframe "
+                               "(NPP x3 + MELPe-1200 analysis + 81-bit packing)" % C,
+                   "channels_per_gpu": C, "channels_total": world * C,
+                   "parallelism": "channel shards, %d GPU(s), no collective" % world},
+        "realtime_factor": value / (world * C),
+    }
+    if not args.full:
+        wl.close()
+        return line if rank == 0 else None
     pipe_equal = bool((ser_bits == wl.bits).all())
     del ser_bits
-    log("encode, pipelined: %.1f ms/step, bits equal to the serialised run: %s"
-        % (1e3 * enc_s / K, pipe_equal))
+    log("bits equal to the serialised run: %s" % pipe_equal)
     hostfed = None
     if not args.no_host_leg and workload_cls is None:
         hostfed = host_leg(rig, C, rank * C, K, W, wl.bits, world)
@@ -817,6 +897,7 @@ def run(args, rank, world, local, backend="nccl", rig_cls=None, workload_cls=Non
         duplex = duplex_leg(rig, wl, C, K, W)
 
     side = {}
+    wl.out = None       # the decoded PCM of every step: no later leg reads it
     if not args.no_side_legs:
         side = side_legs(rig, wl, C, K, W, rank, world)
     wl.close()
@@ -854,7 +935,6 @@ def run(args, rank, world, local, backend="nccl", rig_cls=None, workload_cls=Non
 
     if rank != 0:
         return None
-    value = world * C * K * SF_SECONDS / enc_s
     oc = opcount()
     roof = None
     if oc:
@@ -894,27 +974,15 @@ def run(args, rank, world, local, backend="nccl", rig_cls=None, workload_cls=Non
     base, parity = (None, None)
     if world == 1:
         base, parity = cpu_baseline(args, cpu_bits)
-    return {
-        "metric": "MELPe-1200 channel-seconds encoded/sec (node)",
-        "value": value, "unit": "channel-s/s", "n_gpus": world, "steps": K, "warmup": W,
-        "ms_per_step": 1e3 * enc_s / K, "higher_is_better": True, "scaling": "weak",
-        "step": {"form": "pipelined: superframe k's analysis beside superframe k+1's NPP "
-                         "(melpe_encode_pipe_dev); the timed region holds K NPPs and K analyses",
-                 "ms_per_step_events": pipe_ems,
-                 "ms_per_step_serialised": 1e3 * ser_s / K,
-                 "bits_equal_serialised": pipe_equal},
-        "vs_baseline": None, "dtype": "int16/int32 saturating fixed point",
-        "data": "synthetic (integer speech-like generator csrc/synth.h, run seed %d)" % RUN_SEED,
-        "config": {"workload": "config 4: %d channels per GPU, melpe_a per superframe "
-                               "(NPP x3 + MELPe-1200 analysis + 81-bit packing)" % C,
-                   "channels_per_gpu": C, "channels_total": world * C,
-                   "parallelism": "channel shards, %d GPU(s), no collective" % world},
-        "realtime_factor": value / (world * C),
+    line["step"].update({"ms_per_step_serialised": 1e3 * ser_s / K,
+                         "bits_equal_serialised": pipe_equal})
+    line.update({
         "roofline": roof, "cpu_baseline": base, "decode": dec, "parity_spot_check": parity,
         "strong_scaling": strong, "round_trip": rt, "tx_front_end": tx, "host_fed": hostfed, "duplex": duplex,
         "bitstream_gather": gathered, "voice_crypt": side.get("crypt"), "vad": side.get("vad"),
         "modem": side.get("modem"),
-    }
+    })
+    return line
 
 
 def side_legs(rig, wl, C, K, W, rank, world):
@@ -966,14 +1034,23 @@ def side_legs(rig, wl, C, K, W, rank, world):
 
 MODEM_PKT = 3240          # 48 kHz samples per 81-bit packet (modem/modem.c:136)
 MODEM_CALLS = 15          # Demodulate calls per packet time (216 samples each)
+# the receive side keeps every channel's modulated stream of all the leg's
+# packets on the device, 6,480 bytes per channel and packet, and twice that
+# while the rows are laid out (at 262,144 channels 1.7 GB, then 3.4 GB, per
+# step): the leg runs at most this many timed and warm-up steps, the first
+# ones of the run, so that it fits the device whatever --steps is
+MODEM_STEPS_MAX = 20
+MODEM_WARMUP_MAX = 5
 
 
 def modem_leg(rig, wl, C, K, W, world):
     """PairPhone's pseudo-voice modem on the encoded packets: Modulate (tx.c:271)
     one packet per channel per step, and Demodulate (rx.c:294) the 15 calls
     of one packet time per channel per step on the modulated streams.  Both
-    are byte-moving kernels: roofline = HBM bytes / launch time."""
+    are byte-moving kernels: roofline = HBM bytes / launch time.  At most
+    MODEM_STEPS_MAX timed steps after MODEM_WARMUP_MAX of warm-up."""
     import torch
+    K, W = min(K, MODEM_STEPS_MAX), min(W, MODEM_WARMUP_MAX)
     lib = wl.lib
     sb = lib.melpe_modem_state_bytes()
     st = torch.zeros(C * sb, dtype=torch.uint8, device=rig.dev)
@@ -992,7 +1069,7 @@ def modem_leg(rig, wl, C, K, W, world):
     steps = W + K
     stride = steps * MODEM_PKT + 2048
     stream = torch.zeros((C, stride), dtype=torch.int16, device=rig.dev)
-    pk = wl.bits.transpose(0, 1).contiguous()            # C x steps x 11
+    pk = wl.bits[:steps].transpose(0, 1).contiguous()    # C x steps x 11
     if lib.melpe_modem_reset_dev(st.data_ptr(), C, None, rig.sptr):
         raise RuntimeError(lib.melpe_last_error().decode())
     if lib.melpe_modulate_dev(st.data_ptr(), pk.data_ptr(), stream.data_ptr(), C, steps, None,
@@ -1017,7 +1094,8 @@ def modem_leg(rig, wl, C, K, W, world):
     del stream
     mod_bytes = C * (SF_BYTES + 2 * MODEM_PKT)
     dem_bytes = C * MODEM_CALLS * (2 * 216 + 12) + 2 * C * sb
-    res = {"modulate": {"kernel": "k_modulate", "kernel_ms": mod_kms,
+    res = {"steps": K, "warmup": W,
+           "modulate": {"kernel": "k_modulate", "kernel_ms": mod_kms,
                         "value": world * C * K / mod_s, "unit": "packets/s",
                         "roofline": {"bound": "hbm", "achieved": mod_bytes / (mod_kms / 1e3) / 1e9,
                                      "peak": 8000.0, "unit": "GB/s",

@@ -22,7 +22,7 @@ import pytest
 
 from conftest import ROOT, GOLDEN
 
-DROPIN = os.path.join(ROOT, "build", "dropin")
+DROPIN = os.path.join(ROOT, "oracle", "_ref", "dropin")
 BINS = {"encoder": ("melpe_i", "melpe_a"), "decoder": ("melpe_i", "melpe_s"),
         "melpe_dec": ("melpe_i", "melpe_s")}
 

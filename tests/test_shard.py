@@ -160,7 +160,7 @@ def _bench_worker(rank, world, port, q):
         got["all"] = out.clone()
         return out
     shard.gather_bitstreams = spy
-    args = bench.parse(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--channels", "5",
+    args = bench.parse(["--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--channels", "5",
                         "--total-channels", "13", "--tx-channels", "0", "--no-side-legs",
                         "--no-cpu-baseline"])
     line = bench.run(args, rank, world, rank, rig_cls=CpuRig, workload_cls=FakeWorkload)
@@ -195,6 +195,57 @@ def test_bench_run_world2_gloo():
     assert allbits.shape == (3, 10, 11) and (allbits == want).all()
 
 
+def test_bench_plain_run_is_the_headline_alone():
+    """without --full, bench.run times --steps pipelined steps and returns the
+    headline fields only: no leg, gather, roofline or CPU baseline"""
+    import bench
+    args = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1", "--channels", "5"])
+    assert not args.full and args.dump_outputs is None
+    made = []
+
+    class Spy(FakeWorkload):
+        def __init__(self, *a):
+            super().__init__(*a)
+            made.append(self)
+    line = bench.run(args, 0, 1, 0, rig_cls=CpuRig, workload_cls=Spy)
+    assert len(made) == 1, "a plain run makes the headline's workload only"
+    # the untimed serialised pass, then from fresh state the warm-up and the
+    # timed region: W + K NPPs (superframes 0..3) each
+    assert made[0].calls == 2 * [("npp", s) for s in range(4)]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] is not None
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1
+    assert abs(line["value"] - 5 * 3 * 0.0675 / (line["ms_per_step"] * 3 / 1e3)) < 1e-6 * line["value"]
+    for k in ("roofline", "cpu_baseline", "decode", "strong_scaling", "round_trip", "tx_front_end",
+              "host_fed", "duplex", "bitstream_gather", "voice_crypt", "vad", "modem"):
+        assert k not in line
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs: float32 arrays of the step's bits and of a seeded
+    sample of its in-place NPP output, the same from call to call"""
+    import types
+    import numpy as np
+    import bench
+    C = bench.DUMP_PCM_CHANNELS + 7
+    g = torch.Generator().manual_seed(1)
+    wl = types.SimpleNamespace(
+        rig=types.SimpleNamespace(torch=torch),
+        bits=torch.randint(0, 256, (2, C, 11), dtype=torch.uint8, generator=g),
+        pcm=torch.randint(-32768, 32768, (2, C, 540), dtype=torch.int16, generator=g))
+    for d in ("a", "b"):
+        bench.dump_outputs(wl, 1, str(tmp_path / d))
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("bits", "npp_pcm", "channels")}
+    ch = got["channels"].astype(np.int64)
+    assert len(ch) == bench.DUMP_PCM_CHANNELS and (np.diff(ch) > 0).all() and ch[-1] < C
+    assert got["bits"].dtype == np.float32 and got["npp_pcm"].dtype == np.float32
+    assert np.array_equal(got["bits"], wl.bits[1].numpy().astype(np.float32))
+    assert np.array_equal(got["npp_pcm"], wl.pcm[1].numpy()[ch].astype(np.float32))
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2**20
+    for n in got:
+        assert np.array_equal(got[n], np.load(str(tmp_path / "b" / (n + ".npy"))))
+
+
 def _gpu_bench_worker(rank, world, port, C, q):
     """one rank of bench.run with the real engine; every rank on GPU 0 (the
     one-GPU box), collectives over gloo"""
@@ -221,7 +272,7 @@ def _gpu_bench_worker(rank, world, port, C, q):
         got["all"] = out.cpu().clone()
         return out
     shard.gather_bitstreams = spy
-    args = bench.parse(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--channels", str(C),
+    args = bench.parse(["--full", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--channels", str(C),
                         "--total-channels", "0", "--tx-channels", "0", "--no-side-legs",
                         "--no-cpu-baseline", "--no-decode"])
     line = bench.run(args, rank, world, rank, backend="gloo", rig_cls=SharedGpuRig)

@@ -3,7 +3,7 @@
 # tools/pmc_dump.py into gpurun_out/<tag>/pmc_dump.txt
 #   bash tools/gpu_pmc_passes.sh <tag> <channels> "<counters of pass 1>" "<counters of pass 2>" ...
 cd $GRAFT_REPO_ROOT && T=$1 && C=$2 && shift 2 && O=gpurun_out/$T && mkdir -p $O && export TMPDIR=/tmp &&
-B="bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-leg --no-duplex --no-side-legs --no-decode --total-channels 0 --tx-channels 0 --channels $C" &&
+B="bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-leg --no-duplex --no-side-legs --no-decode --total-channels 0 --tx-channels 0 --channels $C" &&
 i=0 &&
 for p in "$@"; do
   i=$((i+1))
