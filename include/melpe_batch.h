@@ -309,6 +309,54 @@ int melpe_stream_pack(const unsigned char *bits, const uint8_t *votes, uint8_t *
 		      unsigned char *out, uint8_t *lens, int channels, const uint8_t *active);
 long melpe_stream_unpack(const unsigned char *stream, long nbytes, unsigned char *bits,
 			 uint8_t *voiced, long max_sf);
+/* The same format on the device (frame rules: pairphone_amd/csrc/stream_fmt.h).
+ *
+ * melpe_stream_pack_dev is melpe_stream_pack for device buffers, with the
+ * output compacted across channels: d_bits C x 11 and d_votes C in, d_last C
+ * bytes in/out, d_active an optional C-byte mask.  d_offs (C + 1 uint32,
+ * 4-byte aligned) receives the exclusive prefix sum of the frame lengths (11,
+ * 1, or 0 for a channel d_active excludes): channel c's frame is
+ * d_out[d_offs[c] .. d_offs[c + 1]) and d_offs[C] the total.  d_out holds
+ * C x 11 bytes; bytes at and past d_offs[C] are not written.  So the host
+ * function's out[c * 11 .. c * 11 + lens[c]) concatenated in channel order is
+ * d_out[0 .. d_offs[C]).  d_work: melpe_stream_pack_work_bytes(C) bytes of
+ * device memory, 4-byte aligned (the scan's block totals).  No engine, no
+ * allocation and no host synchronisation: three kernels on hip_stream.
+ * C x 11 must fit 32 bits.
+ *
+ * melpe_rx_stream_dev is melpe_dec.c:33-49 for the engine's C channels, one
+ * frame per channel and call.  d_stream: the channels' framed bytes; channel
+ * c's next frame starts at d_stream[d_pos[c]] and its stream ends at
+ * d_end[c] (C uint32 each, 4-byte aligned).  Per channel, by the frame found:
+ *   nothing left (d_pos[c] >= d_end[c], or d_active[c] == 0):
+ *       d_lens[c] = 0, d_voiced[c] = 0; its d_bits row, PCM and decoder
+ *       state are untouched;
+ *   silence (bit 1 of the first byte):
+ *       d_lens[c] = 1, d_voiced[c] = 0, its d_bits row zeroed, its PCM 540
+ *       zero samples (melpe_dec.c:37), decoder state untouched;
+ *   voiced with all 11 bytes before d_end[c]:
+ *       d_lens[c] = 11, d_voiced[c] = 1, its d_bits row the frame with the
+ *       swap undone, its PCM melpe_s of it;
+ *   voiced but cut off by d_end[c]:
+ *       d_lens[c] = 0xFF, d_voiced[c] = 0, nothing else touched.  The call
+ *       still returns 0: the caller reads d_lens (melpe_stream_unpack fails
+ *       for that one stream).
+ * d_pos_next[c] (NULL = not wanted) = d_pos[c] + the bytes consumed (0 for
+ * nothing left and for a cut-off frame); it may be d_pos itself, the cursor
+ * of a recorded stream of many superframes (as melpe_demodulate_dev's pos).
+ * The output of melpe_stream_pack_dev is read with d_pos = d_offs, d_end =
+ * d_offs + 1 and d_pos_next = NULL.  d_sp C x 540 int16 (8-byte aligned),
+ * d_bits C x 11, d_voiced and d_lens C bytes, all out.  The decode is
+ * melpe_decode_dev's with d_voiced as its mask (lane order, both decoder
+ * mappings), and the call is an engine call like it: ordered on hip_stream,
+ * serialised with the engine's other calls. */
+long melpe_stream_pack_work_bytes(int channels);
+int melpe_stream_pack_dev(const void *d_bits, const void *d_votes, void *d_last, void *d_out,
+			  void *d_offs, void *d_work, int channels, const void *d_active,
+			  void *hip_stream);
+int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos,
+			const void *d_end, void *d_pos_next, void *d_sp, void *d_bits,
+			void *d_voiced, void *d_lens, const void *d_active, void *hip_stream);
 const char *melpe_last_error(void);
 
 /* The pseudo-voice BPSK modem, PairPhone's TX step after the voice-frame

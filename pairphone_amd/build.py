@@ -145,7 +145,7 @@ def device_disassembly(obj, arch=None):
 # which faulted on gfx950 (kern.h FLAT_GUARD_BYTES)
 NO_FLAT = ("k_enc_ana", "k_enc_harm", "k_enc_tail", "k_decode", "k_vad", "k_enc_npp", "k_npp",
            "k_demodulate", "k_enc24",
-           "k_dec24", "k_helpers_eval")
+           "k_dec24", "k_helpers_eval", "k_stream")
 
 
 def check_no_flat(objdir):

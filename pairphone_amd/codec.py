@@ -84,6 +84,9 @@ def load_library(path=None):
         "melpe_tx_pipe_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "melpe_stream_pack": (i32, [vp, vp, vp, vp, vp, i32, vp]),
         "melpe_stream_unpack": (ctypes.c_long, [vp, ctypes.c_long, vp, vp, ctypes.c_long]),
+        "melpe_stream_pack_work_bytes": (ctypes.c_long, [i32]),
+        "melpe_stream_pack_dev": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
+        "melpe_rx_stream_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "melpe_encode2400_dev": (i32, [vp, vp, vp, vp, vp]),
         "melpe_decode2400_dev": (i32, [vp, vp, vp, vp, vp]),
         "melpe_encode2400_host": (i32, [vp, vp, vp, vp]),
@@ -188,6 +191,23 @@ def stream_unpack(stream, max_sf=None):
     return bits[:k], voiced[:k]
 
 
+def stream_pack_work_bytes(channels):
+    """bytes of device work memory stream_pack_dev needs for C channels"""
+    n = load_library().melpe_stream_pack_work_bytes(int(channels))
+    _check(n if n < 0 else 0)
+    return n
+
+
+def stream_pack_dev(d_bits, d_votes, d_last, d_out, d_offs, d_work, channels, d_active=None,
+                    stream=None):
+    """stream_pack of one superframe of C channels on the device, the frames
+    compacted across channels: d_out[d_offs[c] : d_offs[c + 1]] is channel
+    c's frame, d_offs (C + 1 uint32) the exclusive prefix sum of the frame
+    lengths (melpe_stream_pack_dev)"""
+    _check(load_library().melpe_stream_pack_dev(d_bits, d_votes, d_last, d_out, d_offs, d_work,
+                                                int(channels), d_active, stream))
+
+
 class Vad:
     """PairPhone's TX voice-activity gate on C channels (vad/vad2.c run on six
     windows per superframe, tx.c:234-239); state per channel = a fresh
@@ -219,6 +239,7 @@ class MelpeEngine:
         self.h = ctypes.c_void_p()
         _check(self.lib.melpe_engine_create(ctypes.byref(self.h), device, channels))
         self.channels = channels
+        self.device = device
 
     def close(self):
         if self.h:
@@ -394,6 +415,67 @@ class MelpeEngine:
 
     def decode_dev(self, d_sp, d_bits, d_active=None, stream=None):
         _check(self.lib.melpe_decode_dev(self.h, d_sp, d_bits, d_active, stream))
+
+    def rx_stream_dev(self, d_stream, d_pos, d_end, d_pos_next, d_sp, d_bits, d_voiced, d_lens,
+                      d_active=None, stream=None):
+        """one VAD-framed frame per channel (melpe_dec.c:33-49): parse at
+        d_pos[c] < d_end[c], 540 zeros for silence, melpe_s for a voiced
+        frame; d_lens[c] = 0 (ended), 1, 11 or 0xFF (truncated voiced frame);
+        d_pos_next (None, or d_pos itself) receives the advanced cursors"""
+        _check(self.lib.melpe_rx_stream_dev(self.h, d_stream, d_pos, d_end, d_pos_next, d_sp,
+                                            d_bits, d_voiced, d_lens, d_active, stream))
+
+    def decode_streams(self, streams):
+        """melpe_dec for C files at once: `streams` is one VAD-framed byte
+        string per channel, of any lengths.  They are uploaded once and
+        rx_stream_dev steps every channel's cursor in place until all have
+        ended.  Returns one int16 array per channel, 540 samples per frame
+        consumed.  Raises RuntimeError naming the channel whose stream ends in
+        a truncated voiced frame.  `self.last_cursors` keeps the final
+        cursors relative to each stream's start (its length when all of it
+        was consumed)."""
+        import torch
+        C = self.channels
+        if len(streams) != C:
+            raise ValueError("decode_streams takes one stream per channel (%d)" % C)
+        sizes = np.array([len(s) for s in streams], np.int64)
+        ends = np.cumsum(sizes)
+        if ends[-1] >= 1 << 32:
+            raise ValueError("the streams together exceed 32-bit offsets")
+        starts = ends - sizes
+        dev = torch.device("cuda:%d" % self.device)
+        blob = np.frombuffer(b"".join(bytes(s) for s in streams) or b"\0", np.uint8)
+        with torch.cuda.device(dev):
+            s = torch.cuda.current_stream(dev).cuda_stream
+            d_stream = torch.from_numpy(blob.copy()).to(dev)
+            d_pos = torch.from_numpy(starts.astype(np.uint32).view(np.int32)).to(dev)
+            d_end = torch.from_numpy(ends.astype(np.uint32).view(np.int32)).to(dev)
+            d_sp = torch.zeros((C, SF_SAMPLES), dtype=torch.int16, device=dev)
+            d_bits = torch.zeros((C, SF_BYTES), dtype=torch.uint8, device=dev)
+            d_voiced = torch.zeros(C, dtype=torch.uint8, device=dev)
+            d_lens = torch.zeros(C, dtype=torch.uint8, device=dev)
+            pos = starts.copy()
+            steps = []      # (lens, PCM) of every step, channels that consumed a frame
+            while (pos < ends).any():
+                self.rx_stream_dev(d_stream.data_ptr(), d_pos.data_ptr(), d_end.data_ptr(),
+                                   d_pos.data_ptr(), d_sp.data_ptr(), d_bits.data_ptr(),
+                                   d_voiced.data_ptr(), d_lens.data_ptr(), None, s)
+                lens = d_lens.cpu().numpy()
+                bad = np.flatnonzero(lens == 0xFF)
+                if len(bad):
+                    raise RuntimeError("decode_streams: the stream of channel %d ends in a "
+                                       "truncated voiced frame" % bad[0])
+                took = np.flatnonzero(lens)
+                steps.append((took, d_sp.cpu().numpy()[took]))
+                pos = pos + lens
+            cur = d_pos.cpu().numpy().view(np.uint32).astype(np.int64)
+        assert np.array_equal(cur, pos), "device cursors and frame lengths disagree"
+        self.last_cursors = cur - starts
+        out = [[] for _ in range(C)]
+        for took, pcm in steps:
+            for i, c in enumerate(took):
+                out[c].append(pcm[i])
+        return [np.concatenate(o) if o else np.zeros(0, np.int16) for o in out]
 
     def synth_seed(self, run_seed, first_channel=0):
         _check(self.lib.melpe_synth_seed(self.h, run_seed, first_channel))

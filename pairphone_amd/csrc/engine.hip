@@ -27,6 +27,7 @@
 #include "synth.h"
 #include "voice_crypt.h"
 #include "vad.h"
+#include "stream_fmt.h"
 #include "ops_eval.h"
 #include "helpers_eval.h"
 #define MODEM_FN __host__ __device__ static inline
@@ -227,6 +228,151 @@ __global__ __launch_bounds__(WAVE) void k_vad_reset(VadState *st, const uint8_t 
 	VadState z;
 	memset(&z, 0, sizeof z);
 	st[c] = z;
+}
+
+/*
+ * The VAD-framed stream format on the device (stream_fmt.h).
+ *
+ * melpe_stream_pack_dev compacts one superframe's frames across channels:
+ * channel c's frame of len(c) = 11, 1 or 0 bytes goes to out[offs[c] ..],
+ * offs = the exclusive prefix sum of len.  The scan is three launches, so no
+ * workgroup ever waits for another: k_stream_len writes each block's total
+ * to work[], k_stream_scan (one block) turns work[] into the blocks' bases,
+ * tile after tile of STREAM_BLOCK totals with a running carry, and
+ * k_stream_scatter scans its block again, adds the block's base and writes
+ * the frames.  Lengths are recomputed from votes and active in both passes,
+ * not stored.
+ */
+#define STREAM_BLOCK 256
+static_assert(STREAM_BLOCK % WAVE == 0 && WAVE == 64, "the scans below are written for wave64");
+
+/* inclusive prefix sum over the wave's 64 lanes, on the DPP lane network:
+ * row_shr:1,2,4,8 scan each row of 16 lanes (bound_ctrl: a lane shifted in
+ * from outside the row reads 0), row_bcast:15 adds a row's total to the next
+ * row (rows 1 and 3), row_bcast:31 adds the lower half's total to rows 2 and
+ * 3.  Every lane of the wave must be active. */
+__device__ static inline unsigned wave_scan_incl(unsigned v)
+{
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);
+	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);
+	return v;
+}
+
+/* exclusive prefix sum of v over the block's STREAM_BLOCK lanes, *total =
+ * their sum; called by every lane of the block.  A caller that loops
+ * synchronises the block before the next call (wsum is reused). */
+__device__ static inline unsigned block_scan_excl(unsigned v, unsigned *total)
+{
+	__shared__ unsigned wsum[STREAM_BLOCK / WAVE];
+	const unsigned inc = wave_scan_incl(v);
+	const int w = threadIdx.x / WAVE;
+	if ((threadIdx.x & (WAVE - 1)) == WAVE - 1)
+		wsum[w] = inc;
+	__syncthreads();
+	unsigned base = 0, t = 0;
+#pragma unroll
+	for (int k = 0; k < STREAM_BLOCK / WAVE; k++) {
+		const unsigned s = wsum[k];
+		base += k < w ? s : 0u;
+		t += s;
+	}
+	*total = t;
+	return base + inc - v;
+}
+
+__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_len(const uint8_t *votes, const uint8_t *active,
+							     uint32_t *work, int channels)
+{
+	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
+	const unsigned len = c < channels ? sfmt_frame_len(!active || active[c], votes[c]) : 0u;
+	unsigned total;
+	block_scan_excl(len, &total);
+	if (threadIdx.x == 0)
+		work[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_scan(uint32_t *work, unsigned nb)
+{
+	unsigned carry = 0;
+	for (unsigned t0 = 0; t0 < nb; t0 += STREAM_BLOCK) {	/* uniform: every lane runs every tile */
+		const unsigned i = t0 + threadIdx.x;
+		const unsigned v = i < nb ? work[i] : 0u;
+		unsigned total;
+		const unsigned ex = block_scan_excl(v, &total);
+		if (i < nb)
+			work[i] = carry + ex;
+		carry += total;
+		__syncthreads();
+	}
+}
+
+__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_scatter(const unsigned char *bits, const uint8_t *votes,
+								 uint8_t *last, unsigned char *out, uint32_t *offs,
+								 const uint32_t *work, int channels,
+								 const uint8_t *active)
+{
+	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
+	const bool in = c < channels;
+	const unsigned vote = in ? votes[c] : 0u;
+	const unsigned len = in ? sfmt_frame_len(!active || active[c], vote) : 0u;
+	unsigned total;
+	const unsigned off = work[blockIdx.x] + block_scan_excl(len, &total);
+	if (!in)
+		return;
+	offs[c] = off;
+	if (c == channels - 1)
+		offs[channels] = off + len;
+	if (len)	/* off + len <= the total <= channels * 11, out's capacity */
+		last[c] = sfmt_pack(bits + c * SFMT_BYTES, vote, last[c], out + off);
+}
+
+/* melpe_dec.c:33-49, the parse of one frame per channel: channel c's frame
+ * starts at stream[pos[c]] and its stream ends at end[c].  pos_next may be
+ * pos itself (a lane touches only its own slot), hence no restrict. */
+__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_parse(const unsigned char *stream, const uint32_t *pos,
+							       const uint32_t *end, uint32_t *pos_next,
+							       unsigned char *bits, uint8_t *voiced, uint8_t *lens,
+							       const uint8_t *active, int channels)
+{
+	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
+	if (c >= channels)
+		return;
+	const uint32_t p = pos[c];
+	unsigned len = 0;
+	if ((!active || active[c]) && p < end[c]) {
+		const unsigned char *f = stream + p;
+		unsigned char *b = bits + c * SFMT_BYTES;
+		len = sfmt_rx_len(f[0], end[c] - p);
+		if (len == 1) {
+#pragma unroll
+			for (int j = 0; j < SFMT_BYTES; j++)
+				b[j] = 0;
+		} else if (len == SFMT_BYTES) {
+			sfmt_unswap(f, b);
+		}
+	}
+	lens[c] = (uint8_t) len;
+	voiced[c] = len == SFMT_BYTES;
+	if (pos_next)
+		pos_next[c] = p + (len == SFMT_TRUNCATED ? 0u : len);
+}
+
+/* melpe_dec.c:37: 540 zero samples for the channels the parse found silent,
+ * one wave per channel, 8 bytes per lane and store */
+static_assert(MELPE_SF_SAMPLES * sizeof(int16_t) % sizeof(uint2) == 0, "a channel's PCM row in 8-byte words");
+__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_zero(uint2 *sp, const uint8_t *lens, int channels)
+{
+	const int words = (int) (MELPE_SF_SAMPLES * sizeof(int16_t) / sizeof(uint2));
+	const long c = blockIdx.x * (long) (STREAM_BLOCK / WAVE) + threadIdx.x / WAVE;
+	if (c >= channels || lens[c] != 1)
+		return;
+	uint2 *row = sp + c * words;
+	for (int i = threadIdx.x & (WAVE - 1); i < words; i += WAVE)
+		row[i] = make_uint2(0u, 0u);
 }
 
 /* Modulate (modem.h, modem/modem.c:136): one wave per (channel, packet).
@@ -2414,21 +2560,9 @@ int melpe_stream_pack(const unsigned char *bits, const uint8_t *votes, uint8_t *
 	for (int c = 0; c < channels; c++) {
 		const unsigned char *b = bits + (size_t) c * MELPE_SF_BYTES;
 		unsigned char *o = out + (size_t) c * MELPE_SF_BYTES;
-		if (active && !active[c]) {
-			lens[c] = 0;
-			continue;
-		}
-		if (votes[c] == 0) {	/* melpe_enc.c:57-59: VAD flag on the carried txbuf[0] */
-			last[c] |= 2;
-			o[0] = last[c];
-			lens[c] = 1;
-		} else {		/* melpe_enc.c:64-70: bytes 0 and 10 swapped */
-			memcpy(o, b, MELPE_SF_BYTES);
-			o[0] = b[10];
-			o[10] = b[0];
-			last[c] = o[0];
-			lens[c] = MELPE_SF_BYTES;
-		}
+		lens[c] = (uint8_t) sfmt_frame_len(!active || active[c], votes[c]);
+		if (lens[c])
+			last[c] = sfmt_pack(b, votes[c], last[c], o);
 	}
 	return 0;
 }
@@ -2441,21 +2575,81 @@ long melpe_stream_unpack(const unsigned char *stream, long nbytes, unsigned char
 	long pos = 0, k = 0;
 	while (pos < nbytes && k < max_sf) {	/* melpe_dec.c:33-48 */
 		unsigned char *b = bits + (size_t) k * MELPE_SF_BYTES;
-		if (stream[pos] & 2) {
-			memset(b, 0, MELPE_SF_BYTES);
-			voiced[k++] = 0;
-			pos += 1;
-			continue;
-		}
-		if (pos + MELPE_SF_BYTES > nbytes)
+		unsigned len = sfmt_rx_len(stream[pos], (unsigned long) (nbytes - pos));
+		if (len == SFMT_TRUNCATED)
 			return fail_msg("melpe_stream_unpack: truncated voiced frame");
-		memcpy(b, stream + pos, MELPE_SF_BYTES);
-		b[0] = stream[pos + 10];
-		b[10] = stream[pos];
-		voiced[k++] = 1;
-		pos += MELPE_SF_BYTES;
+		if (len == 1)
+			memset(b, 0, MELPE_SF_BYTES);
+		else
+			sfmt_unswap(stream + pos, b);
+		voiced[k++] = len != 1;
+		pos += len;
 	}
 	return k;
+}
+
+long melpe_stream_pack_work_bytes(int channels)
+{
+	if (channels <= 0)
+		return fail_msg("melpe_stream_pack_work_bytes: bad arguments");
+	return (long) sizeof(uint32_t) * (((long) channels + STREAM_BLOCK - 1) / STREAM_BLOCK);
+}
+
+int melpe_stream_pack_dev(const void *d_bits, const void *d_votes, void *d_last, void *d_out,
+			  void *d_offs, void *d_work, int channels, const void *d_active,
+			  void *hip_stream)
+{
+	if (!d_bits || !d_votes || !d_last || !d_out || !d_offs || !d_work || channels <= 0)
+		return fail_msg("melpe_stream_pack_dev: bad arguments");
+	if (((uintptr_t) d_offs & 3) || ((uintptr_t) d_work & 3))
+		return fail_msg("melpe_stream_pack_dev: offs and work must be 4-byte aligned");
+	if ((long) channels * SFMT_BYTES > 0xffffffffL)
+		return fail_msg("melpe_stream_pack_dev: the offsets of so many channels exceed 32 bits");
+	hipStream_t s = (hipStream_t) hip_stream;
+	const unsigned nb = (unsigned) (((long) channels + STREAM_BLOCK - 1) / STREAM_BLOCK);
+	k_stream_len<<<nb, STREAM_BLOCK, 0, s>>>((const uint8_t *) d_votes, (const uint8_t *) d_active,
+						 (uint32_t *) d_work, channels);
+	HIPCHK(hipGetLastError());
+	k_stream_scan<<<1, STREAM_BLOCK, 0, s>>>((uint32_t *) d_work, nb);
+	HIPCHK(hipGetLastError());
+	k_stream_scatter<<<nb, STREAM_BLOCK, 0, s>>>(
+		(const unsigned char *) d_bits, (const uint8_t *) d_votes, (uint8_t *) d_last,
+		(unsigned char *) d_out, (uint32_t *) d_offs, (const uint32_t *) d_work, channels,
+		(const uint8_t *) d_active);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+/* melpe_dec.c:33-49 on every channel: the parse (one lane per channel), the
+ * zero fill of the silent channels' PCM, then the engine's decode with the
+ * parse's `voiced` as its mask */
+int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos, const void *d_end,
+			void *d_pos_next, void *d_sp, void *d_bits, void *d_voiced, void *d_lens,
+			const void *d_active, void *hip_stream)
+{
+	if (!e || !d_stream || !d_pos || !d_end || !d_sp || !d_bits || !d_voiced || !d_lens)
+		return fail_msg("melpe_rx_stream_dev: null argument");
+	if (((uintptr_t) d_pos & 3) || ((uintptr_t) d_end & 3) || ((uintptr_t) d_pos_next & 3) ||
+	    ((uintptr_t) d_sp & 7))
+		return fail_msg("melpe_rx_stream_dev: pos, end and pos_next must be 4-byte and "
+				"sp 8-byte aligned");
+	DEVGUARD(e->device);
+	hipStream_t s = (hipStream_t) hip_stream;
+	ENGINE_CALL(e, s);
+	ev_begin(e, s);
+	const int n = e->channels;
+	k_stream_parse<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
+		(const unsigned char *) d_stream, (const uint32_t *) d_pos, (const uint32_t *) d_end,
+		(uint32_t *) d_pos_next, (unsigned char *) d_bits, (uint8_t *) d_voiced,
+		(uint8_t *) d_lens, (const uint8_t *) d_active, n);
+	HIPCHK(hipGetLastError());
+	k_stream_zero<<<(unsigned) (((long) n + STREAM_BLOCK / WAVE - 1) / (STREAM_BLOCK / WAVE)),
+			STREAM_BLOCK, 0, s>>>((uint2 *) d_sp, (const uint8_t *) d_lens, n);
+	HIPCHK(hipGetLastError());
+	HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
+				       (const uint8_t *) d_voiced, s));
+	ev_end(e, s, false);
+	return _call.finish();
 }
 
 }  // extern "C"
