@@ -418,6 +418,24 @@ int melpe_divide_s_sweep_dev(void *d_digest, void *hip_stream);
  * 512 int32 results per lane in d_out.  tests/test_device_helpers.py. */
 int melpe_helpers_eval_dev(int mode, const void *d_src, const void *d_args, void *d_out, int n,
 			   void *hip_stream);
+/* Device self-test of the DSP and math library, function by function
+ * (pairphone_amd/csrc/dsp_eval.h; modes and case layout in
+ * dsp_eval_modes.h).  tests/test_device_dsp.py compares each with the
+ * reference's own function.  All pointers are device pointers; the tables are
+ * brought to the current device first, as engine creation does.
+ *   melpe_dsp_eval_dev: n lanes, lane i on a private copy of its DE_IN int16
+ *     of d_in with the DE_ARGS int32 of d_args, DE_OUT int32 per lane in d_out;
+ *   melpe_dsp_scalar_dev: out[i] = f(args[4i .. 4i+3]), int32, the tables
+ *     from the blob (lds_tables 0) or from the NPP kernels' LDS copy (1, the
+ *     table-reading modes only);
+ *   melpe_dsp_wave_dev: the wave forms, one wavefront per case of DE_WV_IN
+ *     int16 and 4 int32, DE_WV_OUT int32 out. */
+int melpe_dsp_eval_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream);
+int melpe_dsp_scalar_dev(int mode, int lds_tables, const void *d_args, void *d_out, long n,
+			 void *hip_stream);
+int melpe_dsp_wave_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream);
 
 /* Diagnostics: per-stage wave-cycle totals of a profiling build
  * (libmelpe_amd_prof.so, -DMELPE_PROF; tools/stage_prof.py,

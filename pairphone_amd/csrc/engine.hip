@@ -30,6 +30,7 @@
 #include "stream_fmt.h"
 #include "ops_eval.h"
 #include "helpers_eval.h"
+#include "dsp_eval_modes.h"
 #define MODEM_FN __host__ __device__ static inline
 #include "modem.h"
 #include "../../include/melpe.h"
@@ -61,6 +62,7 @@ int melpe_tu_anamw_upload(const void *blob, size_t bytes);
 int melpe_tu_harm_upload(const void *blob, size_t bytes);
 int melpe_tu_dec_upload(const void *blob, size_t bytes);
 int melpe_tu_r24_upload(const void *blob, size_t bytes);
+int melpe_tu_dspeval_upload(const void *blob, size_t bytes);
 int melpe_tu_r24_prof(uint64_t *acc);
 int melpe_tu_npp_prof(uint64_t *acc);
 int melpe_tu_ana_prof(uint64_t *acc);
@@ -80,6 +82,13 @@ int kl_enc_ana_mw(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t
 		  const int *perm, const int *nlive, int nw, uint32_t *lqbuf, AnaGate gate, hipStream_t s);
 size_t kl_enc_ana_mw_lq_words(int n);
 int kl_enc_ana_dbg(EncState *enc, const int16_t *sp, int n, int upto, hipStream_t s);
+/* the function-level parity test (dsp_eval.h): lane and blob-table scalar
+ * modes in k_dsp_eval.hip, the wave forms next to the code they test */
+int kl_dsp_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
+int kl_dsp_scalar(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
+int kl_dsp_scalar_lds(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
+int kl_dsp_wave_fft(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
+int kl_dsp_wave_harm(const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
 int kl_npp_warm(int n, hipStream_t s);
 int kl_ana_warm(int n, hipStream_t s);
 int kl_harm_warm(int n, hipStream_t s);
@@ -1082,7 +1091,8 @@ static int ensure_device_tables(int dev)
 	DEVGUARD(dev);
 	int (*up[])(const void *, size_t) = {melpe_tu_eng_upload, melpe_tu_npp_upload,
 					     melpe_tu_ana_upload, melpe_tu_anamw_upload, melpe_tu_harm_upload,
-					     melpe_tu_dec_upload, melpe_tu_r24_upload};
+					     melpe_tu_dec_upload, melpe_tu_r24_upload,
+					     melpe_tu_dspeval_upload};
 	for (auto f : up)
 		if (int rc = f(melpe_tables_blob, bytes))
 			return fail("table upload", (hipError_t) rc);
@@ -2359,6 +2369,69 @@ int melpe_helpers_eval_dev(int mode, const void *d_src, const void *d_args, void
 	k_helpers_eval<<<grid_for(n), WAVE, 0, (hipStream_t) hip_stream>>>(
 		mode, (const int16_t *) d_src, (const int32_t *) d_args, (int32_t *) d_out, n);
 	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+/* the tables of every TU on the caller's current device (the path engine
+ * creation takes), for the engine-less self-tests that read them */
+static int current_device_tables(void)
+{
+	int dev = 0;
+	HIPCHK(hipGetDevice(&dev));
+	return ensure_device_tables(dev);
+}
+
+int melpe_dsp_eval_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream)
+{
+	if (!d_in || !d_args || !d_out || n < 0 || mode < 0 || mode >= DE_MODE_COUNT)
+		return fail_msg("melpe_dsp_eval_dev: bad arguments");
+	if (n == 0)
+		return 0;
+	if (int rc = current_device_tables())
+		return rc;
+	if (int rc = kl_dsp_eval(mode, (const int16_t *) d_in, (const int32_t *) d_args, (int32_t *) d_out, n,
+				 (hipStream_t) hip_stream))
+		return fail("melpe_dsp_eval_dev", (hipError_t) rc);
+	return 0;
+}
+
+int melpe_dsp_scalar_dev(int mode, int lds_tables, const void *d_args, void *d_out, long n,
+			 void *hip_stream)
+{
+	/* n within int: either form's grid (256 or 64 cases per block) fits */
+	if (!d_args || !d_out || n < 0 || n > 0x7fffffffL || mode < 0 || mode >= DE_SCALAR_COUNT ||
+	    (lds_tables && mode > DE_SCALAR_LDS_LAST))
+		return fail_msg("melpe_dsp_scalar_dev: bad arguments");
+	if (n == 0)
+		return 0;
+	if (int rc = current_device_tables())
+		return rc;
+	int rc = lds_tables ? kl_dsp_scalar_lds(mode, (const int32_t *) d_args, (int32_t *) d_out, n,
+						(hipStream_t) hip_stream)
+			    : kl_dsp_scalar(mode, (const int32_t *) d_args, (int32_t *) d_out, n,
+					    (hipStream_t) hip_stream);
+	if (rc)
+		return fail("melpe_dsp_scalar_dev", (hipError_t) rc);
+	return 0;
+}
+
+int melpe_dsp_wave_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream)
+{
+	if (!d_in || !d_args || !d_out || n < 0 || mode < 0 || mode >= DE_WAVE_COUNT)
+		return fail_msg("melpe_dsp_wave_dev: bad arguments");
+	if (n == 0)
+		return 0;
+	if (int rc = current_device_tables())
+		return rc;
+	int rc = mode == DE_WAVE_FIND_HARM
+			 ? kl_dsp_wave_harm((const int16_t *) d_in, (const int32_t *) d_args, (int32_t *) d_out, n,
+					    (hipStream_t) hip_stream)
+			 : kl_dsp_wave_fft(mode, (const int16_t *) d_in, (const int32_t *) d_args,
+					   (int32_t *) d_out, n, (hipStream_t) hip_stream);
+	if (rc)
+		return fail("melpe_dsp_wave_dev", (hipError_t) rc);
 	return 0;
 }
 

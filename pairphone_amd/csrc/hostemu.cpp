@@ -18,6 +18,7 @@
 #include "ana_mw.h"
 #endif
 #include "helpers_eval.h"
+#include "dsp_eval.h"
 #include "codec2400.h"
 #include "voice_crypt.h"
 #include "vad.h"
@@ -218,6 +219,35 @@ int emu_helpers_eval(int mode, const int16_t *src, const int32_t *args, int32_t 
 		memset(o, 0, sizeof(int32_t) * HE_OUT);
 		he_eval(mode, buf, args[4 * i], args[4 * i + 1], args[4 * i + 2], o);
 	}
+	return 0;
+}
+
+/* host build of the function-level parity test (dsp_eval.h), same layouts
+ * as melpe_dsp_eval_dev / melpe_dsp_scalar_dev */
+int emu_dsp_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n)
+{
+	if (mode < 0 || mode >= DE_MODE_COUNT)
+		return -1;
+	for (int i = 0; i < n; i++) {
+		alignas(4) int16_t b[DE_IN];
+		int32_t r[DE_RET] = {0};
+		memcpy(b, in + (size_t) i * DE_IN, sizeof b);
+		de_eval(mode, b, args + (size_t) i * DE_ARGS, r);
+		int32_t *o = out + (size_t) i * DE_OUT;
+		for (int k = 0; k < DE_RET; k++)
+			o[k] = r[k];
+		for (int k = 0; k < DE_IN; k++)
+			o[DE_RET + k] = b[k];
+	}
+	return 0;
+}
+
+int emu_dsp_scalar(int mode, const int32_t *args, int32_t *out, long n)
+{
+	if (mode < 0 || mode >= DE_SCALAR_COUNT)
+		return -1;
+	for (long i = 0; i < n; i++)
+		out[i] = de_scalar(mode, args[4 * i], args[4 * i + 1], args[4 * i + 2], args[4 * i + 3]);
 	return 0;
 }
 

@@ -16,6 +16,7 @@
  */
 #include "kern.h"
 #include "npp_wave.h"
+#include "dsp_eval_modes.h"
 
 MELPE_TU(harm)
 
@@ -244,5 +245,43 @@ extern "C" int kl_harm_warm(int n, hipStream_t s)
 {
 	k_enc_harm<<<n, WAVE, 0, s>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{});
 	k_enc_tail<<<grid_for(n), WAVE, 0, s>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{});
+	return (int) hipGetLastError();
+}
+
+/* Function-level parity test (dsp_eval_modes.h, wave mode wv_find_harm): one
+ * wave per case, the frame loaded as k_enc_harm loads it, the magnitudes
+ * written behind the row's 256 samples */
+__global__ __launch_bounds__(WAVE) void k_dsp_wave_harm(const int16_t *in, const int32_t *args, int32_t *out,
+							 int n)
+{
+	const int c = blockIdx.x;
+	if (c >= n)
+		return;
+	const int lane = threadIdx.x;
+	__shared__ uint32_t x[512];
+	__shared__ int16_t fsmag[NUM_HARM];
+	/* the codec's pitch range, 20 .. 160 in Q7 (the peak search indexes the
+	 * spectrum by it); a case outside it is left unwritten */
+	const int32_t pitch = args[4 * (size_t) c];
+	if (pitch < 20 * 128 || pitch > 160 * 128)
+		return;
+	WvConst kc;
+	wv_const_init(&kc, lane);
+	const int16_t *w = in + (size_t) c * DE_WV_IN;
+	int16_t v[4];
+#pragma unroll
+	for (int t = 0; t < 4; t++)
+		v[t] = w[lane + WV * t];
+	wv_find_harm(v, fsmag, (Word16) pitch, x, &kc, lane);
+	int32_t *o = out + (size_t) c * DE_WV_OUT;
+	if (lane < DE_RET)
+		o[lane] = 0;
+	for (int k = lane; k < DE_WV_IN; k += WV)
+		o[DE_RET + k] = k >= 256 && k < 256 + NUM_HARM ? fsmag[k - 256] : w[k];
+}
+
+extern "C" int kl_dsp_wave_harm(const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s)
+{
+	k_dsp_wave_harm<<<n, WAVE, 0, s>>>(in, args, out, n);
 	return (int) hipGetLastError();
 }

@@ -22,6 +22,7 @@
 #endif
 #include "kern.h"
 #include "npp_wave.h"
+#include "dsp_eval.h"
 
 MELPE_TU(npp)
 
@@ -133,5 +134,56 @@ extern "C" size_t kl_npp_private(void)
 extern "C" int kl_npp_warm(int n, hipStream_t s)
 {
 	k_enc_npp<<<npp_grid(n), NPP_WG, NPP_LDS_DYN, s>>>(nullptr, nullptr, nullptr, 0);
+	return (int) hipGetLastError();
+}
+
+/* Function-level parity test (dsp_eval.h), the forms that live in this TU.
+ * k_dsp_scalar_lds: the table-reading math functions from the LDS copy of
+ * the tables, staged as the NPP kernels above stage it; one thread per case.
+ * k_dsp_wave_fft: wv_cfft256 / wv_fft_npp, one wave per case, the 256
+ * complex points in LDS. */
+__global__ __launch_bounds__(NPP_WG) void k_dsp_scalar_lds(int mode, const int32_t *args, int32_t *out, long n)
+{
+	NPP_TABLES_IN();
+	long i = blockIdx.x * (long) blockDim.x + threadIdx.x;
+	if (i >= n)
+		return;
+	const int32_t *a = args + 4 * i;
+	out[i] = de_scalar(mode, a[0], a[1], a[2], a[3]);
+}
+
+__global__ __launch_bounds__(NPP_WG) void k_dsp_wave_fft(int mode, const int16_t *in, const int32_t *args,
+							  int32_t *out, int n)
+{
+	__shared__ int16_t d[MELPE_NPP_WG_WAVES][DE_WV_IN];
+	NPP_TABLES_IN();
+	const int w = __builtin_amdgcn_readfirstlane(threadIdx.x / WAVE), lane = threadIdx.x % WAVE;
+	const int c = blockIdx.x * MELPE_NPP_WG_WAVES + w;
+	if (c >= n)
+		return;
+	WvConst kc;
+	wv_const_init(&kc, lane);
+	LANE_LOOP(k, DE_WV_IN)
+		d[w][k] = in[(size_t) c * DE_WV_IN + k];
+	wsync();
+	const Word16 g = mode == 1 ? wv_fft_npp(d[w], (Word16) args[4 * (size_t) c], &kc, lane)
+				   : wv_cfft256(d[w], &kc, lane);
+	int32_t *o = out + (size_t) c * DE_WV_OUT;
+	if (lane < DE_RET)
+		o[lane] = lane == 0 ? g : 0;
+	LANE_LOOP(k, DE_WV_IN)
+		o[DE_RET + k] = d[w][k];
+}
+
+extern "C" int kl_dsp_scalar_lds(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s)
+{
+	k_dsp_scalar_lds<<<(unsigned) ((n + NPP_WG - 1) / NPP_WG), NPP_WG, NPP_LDS_DYN, s>>>(mode, args, out, n);
+	return (int) hipGetLastError();
+}
+
+extern "C" int kl_dsp_wave_fft(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n,
+			       hipStream_t s)
+{
+	k_dsp_wave_fft<<<npp_grid(n), NPP_WG, NPP_LDS_DYN, s>>>(mode, in, args, out, n);
 	return (int) hipGetLastError();
 }
