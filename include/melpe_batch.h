@@ -197,6 +197,51 @@ int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
 int melpe_decode_dev(melpe_engine *e, void *d_sp, const void *d_bits,
 		     const void *d_active, void *hip_stream);
 
+/* The codec's own description of a superframe, as tensors.
+ *
+ * A parameter row is MELPE_PAR_WORDS = 30 int16 per frame, in the order of
+ * the reference's struct melp_param (melpe/sc1200.h:233):
+ *   word 0       pitch (Q7, samples)
+ *   words 1..10  lsf (Q15)
+ *   words 11..12 gain (Q8, dB)
+ *   word 13      jitter (Q15)
+ *   words 14..18 bpvc, the band-pass voicing strengths (Q14)
+ *   word 19      uv_flag (1 = unvoiced)
+ *   words 20..29 fs_mag, the Fourier magnitudes (Q13)
+ * A superframe is C x 3 x 30 int16, channel-major like every other buffer
+ * (frame f of channel c at [(c*3 + f)*30]).  The quantiser indices are
+ * MELPE_QPAR_WORDS = 30 int16 per superframe, C x 30, in the field order of
+ * struct quant_param without its pointers (melpe/sc1200.h:244): pitch_index,
+ * lsf_index[3][4], gain_index[2], jit_index[3], bpvc_index[3], fs_index,
+ * uv_flag[3], msvq_index[4], fsvq_index.  Device row buffers are 4-byte
+ * aligned.  Rows of inactive channels are not written.
+ *
+ * melpe_encode_params: melp_par and quant_par as the last melpe_a of each
+ *   active channel left them (d_qpar / qpar NULL = not wanted).  An engine
+ *   call like the others, so it is ordered after melpe_encode_dev and after
+ *   the pipelined forms (melpe_encode_pipe_dev, melpe_tx_dev, ...) alike.
+ * melpe_decode_params: melp_par as the last melpe_s left it, after
+ *   melpe_decode_dev or melpe_rx_stream_dev.
+ * melpe_parse: melpe_s without the synthesis.  bits (C x 11) in; par as
+ *   melpe_s of those bits would leave melp_par; no PCM.  It runs on the
+ *   channel's decoder state and moves on only what the channel reader and the
+ *   parameter head of the synthesis own (the reader's history, melp_par,
+ *   quant_par, the previous frame's parameters, the noise-gain estimate, the
+ *   erasure flag), not the synthesis filters' state.  So a channel is either
+ *   parsed or decoded from its reset (melpe_engine_reset, which = 2), not
+ *   both -- the same rule as for the 2400 bps mode below. */
+#define MELPE_PAR_WORDS 30
+#define MELPE_QPAR_WORDS 30
+int melpe_encode_params_dev(melpe_engine *e, void *d_par, void *d_qpar, const void *d_active,
+			    void *hip_stream);
+int melpe_decode_params_dev(melpe_engine *e, void *d_par, const void *d_active, void *hip_stream);
+int melpe_parse_dev(melpe_engine *e, void *d_par, const void *d_bits, const void *d_active,
+		    void *hip_stream);
+int melpe_encode_params_host(melpe_engine *e, int16_t *par, int16_t *qpar, const uint8_t *active);
+int melpe_decode_params_host(melpe_engine *e, int16_t *par, const uint8_t *active);
+int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits,
+		     const uint8_t *active);
+
 /* The 2400 bps MELP mode (54 bits per 180-sample frame, in 7 bytes), which
  * the reference compiles but cannot reach through melpe_i (melpe/melpe.c:76
  * pins RATE1200): per active channel, encode2400 = npp of the frame at

@@ -17,6 +17,8 @@ import numpy as np
 SF_SAMPLES = 540
 SF_BYTES = 11
 FRAME_SAMPLES = 180
+PAR_WORDS = 30      # int16 per frame of a parameter row (pairphone_amd/params.py)
+QPAR_WORDS = 30     # int16 per superframe of the quantiser indices
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmelpe_amd.so")
 _lib = None
@@ -67,6 +69,12 @@ def load_library(path=None):
         "melpe_duplex_pipe_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "melpe_decode_host": (i32, [vp, vp, vp, vp]),
         "melpe_decode_dev": (i32, [vp, vp, vp, vp, vp]),
+        "melpe_encode_params_dev": (i32, [vp, vp, vp, vp, vp]),
+        "melpe_decode_params_dev": (i32, [vp, vp, vp, vp]),
+        "melpe_parse_dev": (i32, [vp, vp, vp, vp, vp]),
+        "melpe_encode_params_host": (i32, [vp, vp, vp, vp]),
+        "melpe_decode_params_host": (i32, [vp, vp, vp]),
+        "melpe_parse_host": (i32, [vp, vp, vp, vp]),
         "melpe_npp_host": (i32, [vp, vp, i32, i32, vp]),
         "melpe_npp_dev": (i32, [vp, vp, i32, i32, vp, vp]),
         "melpe_synth_seed": (i32, [vp, u32, u32]),
@@ -352,6 +360,47 @@ class MelpeEngine:
         m = self._mask(active)
         _check(self.lib.melpe_decode_host(self.h, _ptr(sp), _ptr(bits), _ptr(m)))
         return sp
+
+    def _rows(self, out, shape):
+        if out is None:
+            return np.zeros(shape, dtype=np.int16)
+        assert out.dtype == np.int16 and out.shape == shape and out.flags.c_contiguous
+        return out
+
+    def encode_params(self, active=None, par=None, qpar=None):
+        """melp_par and quant_par as the last encode left them: int16
+        [C, 3, 30] parameter rows and [C, 30] quantiser indices
+        (pairphone_amd/params.py names the fields).  Rows of inactive
+        channels keep what `par` / `qpar` hold (zeros when not given)."""
+        par = self._rows(par, (self.channels, 3, PAR_WORDS))
+        qpar = self._rows(qpar, (self.channels, QPAR_WORDS))
+        _check(self.lib.melpe_encode_params_host(self.h, _ptr(par), _ptr(qpar), _ptr(self._mask(active))))
+        return par, qpar
+
+    def decode_params(self, active=None, par=None):
+        """melp_par as the last decode left it: int16 [C, 3, 30]."""
+        par = self._rows(par, (self.channels, 3, PAR_WORDS))
+        _check(self.lib.melpe_decode_params_host(self.h, _ptr(par), _ptr(self._mask(active))))
+        return par
+
+    def parse(self, bits, active=None, par=None):
+        """melpe_s without the synthesis: uint8 [C, 11] -> int16 [C, 3, 30],
+        melp_par as a decode of those bits would leave it, no PCM.  A
+        channel is parsed or decoded from its reset, not both."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        assert bits.shape == (self.channels, SF_BYTES)
+        par = self._rows(par, (self.channels, 3, PAR_WORDS))
+        _check(self.lib.melpe_parse_host(self.h, _ptr(par), _ptr(bits), _ptr(self._mask(active))))
+        return par
+
+    def encode_params_dev(self, d_par, d_qpar=None, d_active=None, stream=None):
+        _check(self.lib.melpe_encode_params_dev(self.h, d_par, d_qpar, d_active, stream))
+
+    def decode_params_dev(self, d_par, d_active=None, stream=None):
+        _check(self.lib.melpe_decode_params_dev(self.h, d_par, d_active, stream))
+
+    def parse_dev(self, d_par, d_bits, d_active=None, stream=None):
+        _check(self.lib.melpe_parse_dev(self.h, d_par, d_bits, d_active, stream))
 
     def encode2400(self, sp, active=None):
         """2400 bps mode: one 180-sample frame per channel. sp: int16 [C, 180],

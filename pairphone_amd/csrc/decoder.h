@@ -1432,21 +1432,19 @@ struct SynFrame {
 	int16_t cur_p[MIX_ORD + 1], cur_n[MIX_ORD + 1];
 };
 
+/* The head of melp_syn that owns the frame's parameters (melp_syn.c:189-224):
+ * the first call's noise-gain start, the noise estimate and suppression on
+ * the gains, the unvoiced fill, the Fourier magnitudes' window, the LSF
+ * clamp.  Nothing after it in melp_syn writes *par, so this is all a
+ * parse-only decoder runs of it (parse_superframe); it moves on noise_gain
+ * and syn_started only.  Returns whether this was the channel's first call
+ * (syn_frame_begin then does the rest of the first call's setup). */
 template <bool R24>
-MD void syn_frame_begin(DecState *D, MelpParam *par, SynFrame &F)
+MD bool syn_par_head(DecState *D, MelpParam *par)
 {
-	int16_t refc[LPC_ORD], lpc[LPC_ORD + 1];
-	MelpParam *prev = &D->prev_par;
-	Word16 t1, t2;
-	if (!D->syn_started) {
+	const bool first = !D->syn_started;
+	if (first) {
 		D->noise_gain = par->gain[NUM_GAINFR - 1];
-		D->prev_tilt = 0;
-		v_zero(D->prev_pcof, MIX_ORD + 1);
-		v_zero(D->prev_ncof, MIX_ORD + 1);
-		D->prev_ncof[MIX_ORD / 2] = SW_MAX_;
-		v_zero(D->disp_del, DISP_ORD);
-		v_zero(D->ase_del, LPC_ORD);
-		v_zero(D->tilt_del, 1);
 		D->syn_started = 1;
 	} else if (!D->erase) {
 		for (int i = 0; i < NUM_GAINFR; i++) {
@@ -1462,6 +1460,24 @@ MD void syn_frame_begin(DecState *D, MelpParam *par, SynFrame &F)
 	if (!par->uv_flag && !D->erase)
 		window_Q(par->fs_mag, g_der.w_fs_inv, par->fs_mag, NUM_HARM, 14);
 	lpc_clmp(par->lsf, 409, LPC_ORD);
+	return first;
+}
+
+template <bool R24>
+MD void syn_frame_begin(DecState *D, MelpParam *par, SynFrame &F)
+{
+	int16_t refc[LPC_ORD], lpc[LPC_ORD + 1];
+	MelpParam *prev = &D->prev_par;
+	Word16 t1, t2;
+	if (syn_par_head<R24>(D, par)) {
+		D->prev_tilt = 0;
+		v_zero(D->prev_pcof, MIX_ORD + 1);
+		v_zero(D->prev_ncof, MIX_ORD + 1);
+		D->prev_ncof[MIX_ORD / 2] = SW_MAX_;
+		v_zero(D->disp_del, DISP_ORD);
+		v_zero(D->ase_del, LPC_ORD);
+		v_zero(D->tilt_del, 1);
+	}
 	lpc_lsp2pred(par->lsf, &lpc[1], LPC_ORD);
 	Word16 lpc_gain = lpc_pred2refl(&lpc[1], refc, LPC_ORD);
 	F.lpc_gain = sqrt_fxp(lpc_gain, 15);
@@ -1832,6 +1848,23 @@ MN void decode_superframe(DecState *D, int16_t *out)
 		if (D->syn_begin > 0 && i < NF - 1)
 			v_copy(&out[(i + 1) * FRAME], D->sigsave, D->syn_begin);
 		DEC_CKPT(i + 1);
+	}
+}
+
+/* melpe_s without the synthesis: D->chbuf (11 bytes) -> D->par[NF] as
+ * melpe_s leaves melp_par.  The reference's melp_par after melpe_s depends
+ * only on low_rate_chn_read and on the parameter head of melp_syn; the one
+ * other write near it, prev_par.pitch at melp_syn.c:252, is overwritten by
+ * prev_par = *par (:466) before anything reads it again.  Moves on only the
+ * reader's and the head's part of the state (rd_*, par, qpar, prev_par,
+ * noise_gain, syn_started, erase, chbuf), all on the excitation side of the
+ * record, so a channel is parsed or decoded from its reset, not both. */
+MN void parse_superframe(DecState *D)
+{
+	D->erase = low_rate_chn_read(D);
+	for (int i = 0; i < NF; i++) {
+		syn_par_head<false>(D, &D->par[i]);
+		D->prev_par = D->par[i];
 	}
 }
 

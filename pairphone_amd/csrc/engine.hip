@@ -63,6 +63,7 @@ int melpe_tu_harm_upload(const void *blob, size_t bytes);
 int melpe_tu_dec_upload(const void *blob, size_t bytes);
 int melpe_tu_r24_upload(const void *blob, size_t bytes);
 int melpe_tu_dspeval_upload(const void *blob, size_t bytes);
+int melpe_tu_par_upload(const void *blob, size_t bytes);
 int melpe_tu_r24_prof(uint64_t *acc);
 int melpe_tu_npp_prof(uint64_t *acc);
 int melpe_tu_ana_prof(uint64_t *acc);
@@ -112,6 +113,11 @@ int kl_enc24(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *act
 	     hipStream_t s);
 int kl_dec24(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
 	     hipStream_t s);
+/* the parameter tap and the parse-only decoder (k_par.hip) */
+int kl_par_tap(const void *rec, size_t stride, size_t off, void *par, void *qpar, const uint8_t *active,
+	       int n, hipStream_t s);
+int kl_parse(DecState *dec, void *par, const uint8_t *bits, const uint8_t *active, int n, hipStream_t s);
+size_t kl_parse_private(void);
 }
 
 /* ------------------------------------------------------------------ */
@@ -1092,7 +1098,7 @@ static int ensure_device_tables(int dev)
 	int (*up[])(const void *, size_t) = {melpe_tu_eng_upload, melpe_tu_npp_upload,
 					     melpe_tu_ana_upload, melpe_tu_anamw_upload, melpe_tu_harm_upload,
 					     melpe_tu_dec_upload, melpe_tu_r24_upload,
-					     melpe_tu_dspeval_upload};
+					     melpe_tu_dspeval_upload, melpe_tu_par_upload};
 	for (auto f : up)
 		if (int rc = f(melpe_tables_blob, bytes))
 			return fail("table upload", (hipError_t) rc);
@@ -1287,7 +1293,10 @@ static int engine_reserve(melpe_engine *e)
 	 * k_enc_harm: one per channel, up to the device's resident waves). */
 	{
 		const size_t lane = kl_ana_private() > kl_harm_private() ? kl_ana_private() : kl_harm_private();
-		const size_t per_wave = (lane > kl_dec_private() ? lane : kl_dec_private()) * WAVE;
+		/* (k_parse's frame, the record's excitation side, is far below
+		 * the decoder's: it never sets the maximum and needs no warm-up) */
+		const size_t dec_lane = kl_dec_private() > kl_parse_private() ? kl_dec_private() : kl_parse_private();
+		const size_t per_wave = (lane > dec_lane ? lane : dec_lane) * WAVE;
 		const size_t mw_wave = kl_ana_mw_private() * WAVE;
 		const size_t ww = kl_npp_private() > kl_harm_wave_private() ? kl_npp_private() : kl_harm_wave_private();
 		const size_t waves = (size_t) (e->channels + WAVE - 1) / WAVE;
@@ -1916,6 +1925,112 @@ int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
 	HIPCHK(hipMemcpyAsync(sp, e->d_pcm, pb, hipMemcpyDeviceToHost, e->stream));
 	HOST_FINISH(e);
 	return 0;
+}
+
+/* The codec parameters as tensors (k_par.hip): the tap on the records of the
+ * last melpe_a / melpe_s, and the parse-only decoder.  which: 0 = encoder
+ * tap, 1 = decoder tap, 2 = parse (d_bits in). */
+#define PAR_ROW_BYTES (sizeof(int16_t) * MELPE_PAR_WORDS * NF)
+#define QPAR_ROW_BYTES (sizeof(int16_t) * MELPE_QPAR_WORDS)
+
+static int params_launch(melpe_engine *e, int which, void *d_par, void *d_qpar, const unsigned char *d_bits,
+			 const uint8_t *d_act, hipStream_t s, bool sync)
+{
+	if (((uintptr_t) d_par | (uintptr_t) d_qpar) & 3)
+		return fail_msg("melpe parameter rows: device buffers must be 4-byte aligned");
+	DEVGUARD(e->device);
+	ENGINE_CALL(e, s);
+	ev_begin(e, s);
+	if (which == 0)
+		HIPCHK((hipError_t) kl_par_tap(e->d_enc, sizeof(EncState), offsetof(EncState, a) + offsetof(EncAna, par),
+					       d_par, d_qpar, d_act, e->channels, s));
+	else if (which == 1)
+		HIPCHK((hipError_t) kl_par_tap(e->d_dec, sizeof(DecState), offsetof(DecState, par), d_par, nullptr,
+					       d_act, e->channels, s));
+	else
+		HIPCHK((hipError_t) kl_parse(e->d_dec, d_par, d_bits, d_act, e->channels, s));
+	ev_end(e, s, sync);
+	return _call.finish();
+}
+
+int melpe_encode_params_dev(melpe_engine *e, void *d_par, void *d_qpar, const void *d_active,
+			    void *hip_stream)
+{
+	if (!e || !d_par)
+		return fail_msg("melpe_encode_params_dev: null argument");
+	return params_launch(e, 0, d_par, d_qpar, nullptr, (const uint8_t *) d_active, (hipStream_t) hip_stream,
+			     false);
+}
+
+int melpe_decode_params_dev(melpe_engine *e, void *d_par, const void *d_active, void *hip_stream)
+{
+	if (!e || !d_par)
+		return fail_msg("melpe_decode_params_dev: null argument");
+	return params_launch(e, 1, d_par, nullptr, nullptr, (const uint8_t *) d_active, (hipStream_t) hip_stream,
+			     false);
+}
+
+int melpe_parse_dev(melpe_engine *e, void *d_par, const void *d_bits, const void *d_active,
+		    void *hip_stream)
+{
+	if (!e || !d_par || !d_bits)
+		return fail_msg("melpe_parse_dev: null argument");
+	return params_launch(e, 2, d_par, nullptr, (const unsigned char *) d_bits, (const uint8_t *) d_active,
+			     (hipStream_t) hip_stream, false);
+}
+
+/* the host forms stage the rows in d_pcm (C x 1,080 bytes: a channel's par
+ * row is 180 bytes, its qpar row 60, the qpar rows after all par rows) */
+static int params_host(melpe_engine *e, int which, int16_t *par, int16_t *qpar, const unsigned char *bits,
+		       const uint8_t *active)
+{
+	DEVGUARD(e->device);
+	HOST_LOCK(e);
+	ENGINE_WAIT(e);
+	static_assert(PAR_ROW_BYTES + QPAR_ROW_BYTES <= sizeof(int16_t) * MELPE_SF_SAMPLES && PAR_ROW_BYTES % 4 == 0,
+		      "the rows fit the PCM staging buffer");
+	const size_t pb = PAR_ROW_BYTES * (size_t) e->channels, qb = QPAR_ROW_BYTES * (size_t) e->channels;
+	char *d_par = (char *) e->d_pcm, *d_qpar = qpar ? d_par + pb : nullptr;
+	int rc;
+	const uint8_t *m = stage_mask(e, active, &rc);
+	if (rc)
+		return rc;
+	if (bits)
+		HIPCHK(hipMemcpyAsync(e->d_bits, bits, (size_t) 11 * e->channels, hipMemcpyHostToDevice, e->stream));
+	if (active) {	/* inactive channels keep the caller's rows */
+		HIPCHK(hipMemcpyAsync(d_par, par, pb, hipMemcpyHostToDevice, e->stream));
+		if (qpar)
+			HIPCHK(hipMemcpyAsync(d_qpar, qpar, qb, hipMemcpyHostToDevice, e->stream));
+	}
+	rc = params_launch(e, which, d_par, d_qpar, e->d_bits, m, e->stream, true);
+	if (rc)
+		return rc;
+	HIPCHK(hipMemcpyAsync(par, d_par, pb, hipMemcpyDeviceToHost, e->stream));
+	if (qpar)
+		HIPCHK(hipMemcpyAsync(qpar, d_qpar, qb, hipMemcpyDeviceToHost, e->stream));
+	HOST_FINISH(e);
+	return 0;
+}
+
+int melpe_encode_params_host(melpe_engine *e, int16_t *par, int16_t *qpar, const uint8_t *active)
+{
+	if (!e || !par)
+		return fail_msg("melpe_encode_params_host: null argument");
+	return params_host(e, 0, par, qpar, nullptr, active);
+}
+
+int melpe_decode_params_host(melpe_engine *e, int16_t *par, const uint8_t *active)
+{
+	if (!e || !par)
+		return fail_msg("melpe_decode_params_host: null argument");
+	return params_host(e, 1, par, nullptr, nullptr, active);
+}
+
+int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits, const uint8_t *active)
+{
+	if (!e || !par || !bits)
+		return fail_msg("melpe_parse_host: null argument");
+	return params_host(e, 2, par, nullptr, bits, active);
 }
 
 /* 2400 bps mode (codec2400.h): NPP of one 180-sample frame at RATE2400

@@ -262,6 +262,28 @@ int emu_decode(emu_engine *e, int16_t *sp, const unsigned char *bits)
 	return 0;
 }
 
+/* the parse-only decoder as k_parse runs it (decoder.h parse_superframe):
+ * bits (C x 11) in, melp_par as melpe_s leaves it (C x 3 x 30 int16) out.
+ * The lane's copy holds the excitation side of the record only; the rest is
+ * a pattern, which must come back untouched. */
+int emu_parse(emu_engine *e, int16_t *par_out, const unsigned char *bits)
+{
+	static DecState W;
+	for (int c = 0; c < e->channels; c++) {
+		DecState *D = &e->dec[c];
+		memset(&W, 0x5a + (c & 7), sizeof W);
+		memcpy(&W, D, DEC_B_BEG);
+		memcpy(W.chbuf, bits + (size_t) c * 11, 11);
+		parse_superframe(&W);
+		for (size_t k = DEC_B_BEG; k < sizeof W; k++)
+			if (((const unsigned char *) &W)[k] != (unsigned char) (0x5a + (c & 7)))
+				return -1;
+		memcpy(D, &W, DEC_B_BEG);
+		memcpy(par_out + (size_t) c * NF * 30, D->par, sizeof(D->par));
+	}
+	return 0;
+}
+
 #if !defined(MELPE_OPCOUNT)
 /* the two-wave decoder (decoder.h dec2_phase) as k_decode2 runs it: wave A
  * and wave B each on a private copy of the record, phase by phase, the two
