@@ -299,6 +299,83 @@ int melpe_voice_crypt_dev(void *d_pkts, const void *d_counters, const void *d_ke
 int melpe_voice_crypt_host(unsigned char *pkts, const uint32_t *counters,
 			   const unsigned char *keys, const uint8_t *invert, int channels,
 			   int packets, int dir);
+
+/* The work-stage packet layer between the codec and the modem: PairPhone's
+ * MakeCtr (crp.c:789-838, MakePkt at step 6 and above, tx.c:269) and
+ * ProcessCtr (crp.c:842-982, ProcessPkt at step 5 and above, rx.c:340).  TX
+ * advances the packet counter, encrypts voiced superframes and replaces
+ * silent ones by a control packet (counter twice, 4-bit tag, 8-bit Keccak
+ * authenticator, three Golay(24,12) words).  RX tells control from voice,
+ * resynchronises cnt_in to the far end's counter (fast, or slowly through
+ * soft bits), watches for a far-end reset and decrypts voice with the counter
+ * it has just corrected.  So the chain melpe_tx_dev -> melpe_link_tx_dev ->
+ * melpe_modulate_dev ... melpe_demodulate_dev -> melpe_link_rx_dev ->
+ * melpe_decode_dev stays on the device.
+ *
+ * state: C records of melpe_link_state_bytes() = 256 bytes (device memory,
+ * 4-byte aligned, little-endian), the file statics of crp.c:73-88 the two
+ * functions read or write.  The caller writes them (after its key exchange)
+ * and may read them at any time:
+ *     0  uint32 cnt_out     counter of outgoing packets
+ *     4  uint32 cnt_in      synchronised counter of incoming packets
+ *     8  float  finv        channel polarity (< 0: inverted)
+ *    12  float  fcrc        soft level of the far-end-reset detector
+ *    16  int32  step        stage of the connection
+ *    20  scratch[6]         udata[0..5] as the channel's last ProcessCtr left
+ *                           them (RX only; zero in a fresh record): the bytes
+ *                           an uncorrectable block leaves stale under the
+ *                           crc8 that drives fcrc (crp.c:873-875)
+ *    26  reserved, zero (6 bytes)
+ *    32  skey[32]           [0..15] encrypts, [16..31] decrypts
+ *    64  akey[32]           [0..15] our authenticator key, [16..31] theirs
+ *    96  float  fdata[32]   soft bits of the counter delta
+ *   224  reserved, zero (32 bytes)
+ * A TX record and an RX record are the two ends' own statics: a loopback
+ * mirrors the keys (the RX side's skey[16..31] = the TX side's skey[0..15],
+ * likewise akey).  Each direction has its own record, so the RX scratch bytes
+ * are those of the channel's own previous RX packet, where one reference
+ * process would also see its TX calls' (pairphone_amd/csrc/link.h).
+ *
+ * pkts: C x K x 11 bytes in and out, as in melpe_voice_crypt_dev; the device
+ *   pointer 4-byte aligned.  Channel c's K packets are processed in order.
+ * voiced (TX): C x K bytes, bit 0 = the VAD flag (txbuf[11], tx.c:241); NULL
+ *   = every packet is silence.
+ * ret: C x K int32, the reference's return value: TX cnt_out at step 8, else
+ *   -3; RX -3 for voice, else the authentication level 0..8 (0 also for the
+ *   reset exits).  Or one of two statuses the reference never returns, where
+ *   it would enter the key-exchange stages, which stay on the host:
+ *     MELPE_LINK_REKEY  TX packet whose incremented cnt_out would exceed
+ *       65,534 (crp.c:808): that packet and the channel's later packets of
+ *       the call are left untouched, the record keeps its pre-packet cnt_out;
+ *     MELPE_LINK_STAGE  TX at step < 6, RX at step < 5: record and packets
+ *       untouched; ret gets the status (and RX voice gets 0) for every packet
+ *       of the channel.
+ *   The host then does the key exchange and writes a new record.
+ * voice (RX, optional): C x K bytes, ret == -3.  For K = 1 it is
+ *   melpe_decode_dev's mask: melpe_s for voice, 540 zeros otherwise
+ *   (rx.c:356-360).
+ * active: optional C-byte mask; an inactive channel keeps its record,
+ *   packets and outputs.
+ * The *_dev forms allocate nothing and do not synchronise; the *_host forms
+ * take host buffers, copy and run the same kernels. */
+#define MELPE_LINK_REKEY (-100)
+#define MELPE_LINK_STAGE (-101)
+int melpe_link_state_bytes(void);
+int melpe_link_tx_dev(void *d_state, void *d_pkts, const void *d_voiced, void *d_ret,
+		      int channels, int packets, const void *d_active, void *hip_stream);
+int melpe_link_rx_dev(void *d_state, void *d_pkts, void *d_ret, void *d_voice,
+		      int channels, int packets, const void *d_active, void *hip_stream);
+int melpe_link_tx_host(void *state, unsigned char *pkts, const uint8_t *voiced, int32_t *ret,
+		       int channels, int packets, const uint8_t *active);
+int melpe_link_rx_host(void *state, unsigned char *pkts, int32_t *ret, uint8_t *voice,
+		       int channels, int packets, const uint8_t *active);
+/* Device Golay(24,12) (pairphone_amd/csrc/golay.h) over its whole domain:
+ * d_enc (4,096 uint32) gets the codewords, d_digest (256 uint64) gets, for
+ * bucket b = v >> 16, the sum over its 65,536 received words v of
+ * decode(v) * (v * 0x9E3779B97F4A7C15 + 1) mod 2^64.  tests/test_link.py
+ * compares with the same sums over the reference's fec_golay2412.c. */
+int melpe_golay_sweep_dev(void *d_enc, void *d_digest, void *hip_stream);
+
 /* Voice activity detection, the TX gate in front of melpe_a: PairPhone runs
  * the AMR VAD option 2 (vad/vad2.c:203) on six 80-sample windows of every
  * superframe, at offsets 10, 100, ..., 460 (tx.c:234-239,

@@ -86,6 +86,12 @@ def load_library(path=None):
         "melpe_prof_read": (i32, [vp, i32]),
         "melpe_voice_crypt_dev": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),
         "melpe_voice_crypt_host": (i32, [vp, vp, vp, vp, i32, i32, i32]),
+        "melpe_link_state_bytes": (i32, []),
+        "melpe_link_tx_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+        "melpe_link_rx_dev": (i32, [vp, vp, vp, vp, i32, i32, vp, vp]),
+        "melpe_link_tx_host": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+        "melpe_link_rx_host": (i32, [vp, vp, vp, vp, i32, i32, vp]),
+        "melpe_golay_sweep_dev": (i32, [vp, vp, vp]),
         "melpe_vad_state_bytes": (i32, []),
         "melpe_vad_reset_dev": (i32, [vp, i32, vp, vp]),
         "melpe_vad_dev": (i32, [vp, vp, vp, i32, vp, vp]),
@@ -217,6 +223,92 @@ def stream_pack_dev(d_bits, d_votes, d_last, d_out, d_offs, d_work, channels, d_
     lengths (melpe_stream_pack_dev)"""
     _check(load_library().melpe_stream_pack_dev(d_bits, d_votes, d_last, d_out, d_offs, d_work,
                                                 int(channels), d_active, stream))
+
+
+LINK_REKEY = -100    # MELPE_LINK_REKEY: the call-time limit, the host exchanges new keys
+LINK_STAGE = -101    # MELPE_LINK_STAGE: the channel is not at the work stage
+
+# one channel's link record (include/melpe_batch.h)
+LINK_RECORD = np.dtype([("cnt_out", "<u4"), ("cnt_in", "<u4"), ("finv", "<f4"), ("fcrc", "<f4"),
+                        ("step", "<i4"), ("scratch", "u1", 6), ("rsv0", "u1", 6), ("skey", "u1", 32), ("akey", "u1", 32),
+                        ("fdata", "<f4", 32), ("rsv1", "<u4", 8)])
+
+
+class Link:
+    """PairPhone's work-stage packet layer on C channels: MakeCtr on the way
+    out (`tx`), ProcessCtr on the way in (`rx`), crp.c:789-982.  `state` is
+    the C x 256 uint8 tensor of the channels' records (one end of each call:
+    the far end is another Link whose keys mirror this one's).  Returns are
+    the reference's, or LINK_REKEY / LINK_STAGE where the host's key exchange
+    has to take over."""
+
+    def __init__(self, channels):
+        self.lib = load_library()
+        self.C = int(channels)
+        nb = self.lib.melpe_link_state_bytes()
+        if nb != LINK_RECORD.itemsize:
+            raise RuntimeError("libmelpe_amd: link record of %d bytes" % nb)
+        self.state = np.zeros((self.C, nb), np.uint8)
+
+    def setup(self, cnt_out, cnt_in, step, finv, skey, akey):
+        """packs fresh records: scalars or C values each, keys C x 32 bytes
+        (skey[0..15] encrypts, [16..31] decrypts; akey likewise); fcrc and
+        the soft bits start at zero"""
+        r = np.zeros(self.C, LINK_RECORD)
+        r["cnt_out"], r["cnt_in"], r["step"], r["finv"] = cnt_out, cnt_in, step, finv
+        r["skey"] = np.asarray(skey, np.uint8).reshape(self.C, 32)
+        r["akey"] = np.asarray(akey, np.uint8).reshape(self.C, 32)
+        self.state[:] = r.view(np.uint8).reshape(self.C, -1)
+        return self
+
+    def fields(self):
+        """the records as a structured array (a copy): cnt_out, cnt_in, finv,
+        fcrc, step, scratch (RX: udata[0..5] of the last packet), skey, akey,
+        fdata"""
+        return self.state.reshape(-1).view(LINK_RECORD).copy()
+
+    def _pkts(self, pkts):
+        pkts = np.ascontiguousarray(pkts, dtype=np.uint8)
+        if pkts.ndim == 2:
+            pkts = pkts[:, None, :]
+        if pkts.ndim != 3 or pkts.shape[0] != self.C or pkts.shape[2] != SF_BYTES:
+            raise ValueError("packets must be C x 11 or C x K x 11 bytes")
+        return pkts.copy()
+
+    def _mask(self, active):
+        return None if active is None else np.ascontiguousarray(active, np.uint8).reshape(self.C)
+
+    def tx(self, pkts, voiced, active=None):
+        """(packets, returns C x K): voiced superframes encrypted, silent ones
+        (voiced 0, or voiced None = all) replaced by control packets"""
+        out = self._pkts(pkts)
+        K = out.shape[1]
+        v = None if voiced is None else np.ascontiguousarray(voiced, np.uint8).reshape(self.C, K)
+        ret = np.zeros((self.C, K), np.int32)
+        _check(self.lib.melpe_link_tx_host(_ptr(self.state), _ptr(out), _ptr(v), _ptr(ret), self.C, K,
+                                           _ptr(self._mask(active))))
+        return out, ret
+
+    def rx(self, pkts, active=None):
+        """(packets, returns C x K, voice C x K): voice packets decrypted in
+        place and marked 1 in `voice` (the decoder's mask), the rest left"""
+        out = self._pkts(pkts)
+        K = out.shape[1]
+        ret = np.zeros((self.C, K), np.int32)
+        voice = np.zeros((self.C, K), np.uint8)
+        _check(self.lib.melpe_link_rx_host(_ptr(self.state), _ptr(out), _ptr(ret), _ptr(voice), self.C, K,
+                                           _ptr(self._mask(active))))
+        return out, ret, voice
+
+    def tx_dev(self, d_state, d_pkts, d_voiced, d_ret, packets=1, d_active=None, stream=None):
+        """melpe_link_tx_dev on device pointers (d_state: this Link's records
+        uploaded by the caller)"""
+        _check(self.lib.melpe_link_tx_dev(d_state, d_pkts, d_voiced, d_ret, self.C, int(packets), d_active,
+                                          stream))
+
+    def rx_dev(self, d_state, d_pkts, d_ret, d_voice=None, packets=1, d_active=None, stream=None):
+        _check(self.lib.melpe_link_rx_dev(d_state, d_pkts, d_ret, d_voice, self.C, int(packets), d_active,
+                                          stream))
 
 
 class Vad:

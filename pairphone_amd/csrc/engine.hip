@@ -118,6 +118,12 @@ int kl_par_tap(const void *rec, size_t stride, size_t off, void *par, void *qpar
 	       int n, hipStream_t s);
 int kl_parse(DecState *dec, void *par, const uint8_t *bits, const uint8_t *active, int n, hipStream_t s);
 size_t kl_parse_private(void);
+/* the link's packet layer and the Golay sweep (k_link.hip) */
+int kl_link_tx(void *st, void *pkts, const void *voiced, void *ret, const void *active, int channels,
+	       int packets, hipStream_t s);
+int kl_link_rx(void *st, void *pkts, void *ret, void *voice, const void *active, int channels, int packets,
+	       hipStream_t s);
+int kl_golay_sweep(void *enc, void *digest, hipStream_t s);
 }
 
 /* ------------------------------------------------------------------ */
@@ -2601,6 +2607,121 @@ int melpe_voice_crypt_host(unsigned char *pkts, const uint32_t *counters,
 	return rc;
 }
 
+
+/* the link's packet layer (k_link.hip, link.h) */
+#define LINK_STATE_BYTES 256
+
+int melpe_link_state_bytes(void)
+{
+	return LINK_STATE_BYTES;
+}
+
+/* argument errors, refused before any HIP call */
+static int link_args(const char *who, const void *state, const void *pkts, const void *ret, int channels,
+		     int packets, bool dev)
+{
+	const std::string w(who);
+	if (channels <= 0 || packets <= 0)
+		return fail_msg(w + ": channels and packets must be positive");
+	if (!state)
+		return fail_msg(w + ": null state pointer");
+	if (!pkts)
+		return fail_msg(w + ": null packet pointer");
+	if (!ret)
+		return fail_msg(w + ": null return-value pointer");
+	if ((uintptr_t) state & 3)
+		return fail_msg(w + ": state must be 4-byte aligned");
+	if (dev && (((uintptr_t) pkts & 3) || ((uintptr_t) ret & 3)))
+		return fail_msg(w + ": packets and return values must be 4-byte aligned");
+	if ((long) channels * packets > 0x7fffffffL / VC_PKT_BYTES)
+		return fail_msg(w + ": too many packets");
+	return 0;
+}
+
+int melpe_link_tx_dev(void *d_state, void *d_pkts, const void *d_voiced, void *d_ret, int channels,
+		      int packets, const void *d_active, void *hip_stream)
+{
+	if (int rc = link_args("melpe_link_tx_dev", d_state, d_pkts, d_ret, channels, packets, true))
+		return rc;
+	if (int rc = kl_link_tx(d_state, d_pkts, d_voiced, d_ret, d_active, channels, packets,
+				(hipStream_t) hip_stream))
+		return fail("melpe_link_tx_dev", (hipError_t) rc);
+	return 0;
+}
+
+int melpe_link_rx_dev(void *d_state, void *d_pkts, void *d_ret, void *d_voice, int channels, int packets,
+		      const void *d_active, void *hip_stream)
+{
+	if (int rc = link_args("melpe_link_rx_dev", d_state, d_pkts, d_ret, channels, packets, true))
+		return rc;
+	if (int rc = kl_link_rx(d_state, d_pkts, d_ret, d_voice, d_active, channels, packets,
+				(hipStream_t) hip_stream))
+		return fail("melpe_link_rx_dev", (hipError_t) rc);
+	return 0;
+}
+
+/* host buffers: one staged upload per tensor, the same kernels, and back.
+ * flag = voiced (TX, in) or voice (RX, out), C x K bytes, optional */
+static int link_host(bool tx, void *state, unsigned char *pkts, uint8_t *flag, int32_t *ret, int channels,
+		     int packets, const uint8_t *active)
+{
+	const char *who = tx ? "melpe_link_tx_host" : "melpe_link_rx_host";
+	if (int rc = link_args(who, state, pkts, ret, channels, packets, false))
+		return rc;
+	const size_t n = (size_t) channels * packets;
+	const size_t sb = (size_t) channels * LINK_STATE_BYTES, rb = n * 4, pb = (n * VC_PKT_BYTES + 3) & ~(size_t) 3;
+	const size_t fb = (n + 3) & ~(size_t) 3;
+	int dev = 0;
+	HIPCHK(hipGetDevice(&dev));
+	std::lock_guard<std::mutex> lk(g_stage[dev & 63].mu);
+	unsigned char *d = nullptr;
+	if (int r = stage_get(dev, sb + rb + pb + fb + channels, (void **) &d))
+		return r;
+	unsigned char *ds = d, *dr = ds + sb, *dp = dr + rb, *df = dp + pb, *da = df + fb;
+	hipError_t he;
+	/* an inactive or refused channel keeps its outputs: ret (and RX voice) go up too */
+	if ((he = hipMemcpy(ds, state, sb, hipMemcpyHostToDevice)) != hipSuccess ||
+	    (he = hipMemcpy(dr, ret, rb, hipMemcpyHostToDevice)) != hipSuccess ||
+	    (he = hipMemcpy(dp, pkts, n * VC_PKT_BYTES, hipMemcpyHostToDevice)) != hipSuccess ||
+	    (flag && (he = hipMemcpy(df, flag, n, hipMemcpyHostToDevice)) != hipSuccess) ||
+	    (active && (he = hipMemcpy(da, active, channels, hipMemcpyHostToDevice)) != hipSuccess))
+		return fail((std::string(who) + ": upload").c_str(), he);
+	int rc = tx ? melpe_link_tx_dev(ds, dp, flag ? df : nullptr, dr, channels, packets, active ? da : nullptr,
+					nullptr)
+		    : melpe_link_rx_dev(ds, dp, dr, flag ? df : nullptr, channels, packets,
+					active ? da : nullptr, nullptr);
+	if (rc)
+		return rc;
+	if ((he = hipMemcpy(state, ds, sb, hipMemcpyDeviceToHost)) != hipSuccess ||
+	    (he = hipMemcpy(ret, dr, rb, hipMemcpyDeviceToHost)) != hipSuccess ||
+	    (he = hipMemcpy(pkts, dp, n * VC_PKT_BYTES, hipMemcpyDeviceToHost)) != hipSuccess ||
+	    (!tx && flag && (he = hipMemcpy(flag, df, n, hipMemcpyDeviceToHost)) != hipSuccess))
+		return fail((std::string(who) + ": download").c_str(), he);
+	return 0;
+}
+
+int melpe_link_tx_host(void *state, unsigned char *pkts, const uint8_t *voiced, int32_t *ret, int channels,
+		       int packets, const uint8_t *active)
+{
+	return link_host(true, state, pkts, (uint8_t *) voiced, ret, channels, packets, active);
+}
+
+int melpe_link_rx_host(void *state, unsigned char *pkts, int32_t *ret, uint8_t *voice, int channels,
+		       int packets, const uint8_t *active)
+{
+	return link_host(false, state, pkts, voice, ret, channels, packets, active);
+}
+
+int melpe_golay_sweep_dev(void *d_enc, void *d_digest, void *hip_stream)
+{
+	if (!d_enc || !d_digest)
+		return fail_msg("melpe_golay_sweep_dev: null argument");
+	if (((uintptr_t) d_enc & 3) || ((uintptr_t) d_digest & 7))
+		return fail_msg("melpe_golay_sweep_dev: misaligned argument");
+	if (int rc = kl_golay_sweep(d_enc, d_digest, (hipStream_t) hip_stream))
+		return fail("melpe_golay_sweep_dev", (hipError_t) rc);
+	return 0;
+}
 
 int melpe_vad_state_bytes(void)
 {

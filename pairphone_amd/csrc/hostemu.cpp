@@ -21,6 +21,7 @@
 #include "dsp_eval.h"
 #include "codec2400.h"
 #include "voice_crypt.h"
+#include "link.h"
 #include "vad.h"
 #include "modem.h"
 
@@ -419,6 +420,77 @@ int emu_voice_crypt(unsigned char *pkts, const uint32_t *counters, const unsigne
 		for (int k = 0; k < packets; k++)
 			vc_apply(pkts + ((size_t) c * packets + k) * VC_PKT_BYTES,
 				 counters[c] + (uint32_t) k, key, dir, invert ? invert[c] : 0);
+	}
+	return 0;
+}
+
+/* host build of the link's packet layer (link.h), same layout and statuses
+ * as melpe_link_tx_host / melpe_link_rx_host */
+int emu_link_tx(unsigned char *state, unsigned char *pkts, const uint8_t *voiced, int32_t *ret,
+		int channels, int packets, const uint8_t *active)
+{
+	LinkState *st = (LinkState *) state;
+	for (int c = 0; c < channels; c++) {
+		if (active && !active[c])
+			continue;
+		for (int k = 0; k < packets; k++) {
+			const size_t i = (size_t) c * packets + k;
+			ret[i] = link_make_ctr(&st[c], pkts + i * VC_PKT_BYTES, voiced ? voiced[i] : 0);
+		}
+	}
+	return 0;
+}
+
+int emu_link_rx(unsigned char *state, unsigned char *pkts, int32_t *ret, uint8_t *voice, int channels,
+		int packets, const uint8_t *active)
+{
+	LinkState *st = (LinkState *) state;
+	for (int c = 0; c < channels; c++) {
+		if (active && !active[c])
+			continue;
+		LinkRx R;
+		link_rx_load(&R, &st[c]);
+		for (int k = 0; k < packets; k++) {
+			const size_t i = (size_t) c * packets + k;
+			int r = LINK_STAGE;
+			if (R.step >= 5) {
+				uint64_t lo, hi;
+				bool wr;
+				link_pkt_load(pkts + i * VC_PKT_BYTES, &lo, &hi);
+				r = link_process_ctr(&R, &lo, &hi, &wr);
+				if (wr)
+					link_pkt_store(pkts + i * VC_PKT_BYTES, lo, hi);
+			}
+			ret[i] = r;
+			if (voice)
+				voice[i] = r == -3;
+		}
+		if (R.step >= 5)
+			link_rx_store(&st[c], &R);
+	}
+	return 0;
+}
+
+unsigned emu_golay_encode(unsigned m)
+{
+	return fec_golay2412_encode_symbol(m);
+}
+
+unsigned emu_golay_decode(unsigned r)
+{
+	return fec_golay2412_decode_symbol(r);
+}
+
+/* the sweep of melpe_golay_sweep_dev on the host */
+int emu_golay_sweep(uint32_t *enc, uint64_t *digest)
+{
+	for (uint32_t m = 0; m < 4096; m++)
+		enc[m] = fec_golay2412_encode_symbol(m);
+	for (uint32_t b = 0; b < 256; b++) {
+		uint64_t h = 0;
+		for (uint32_t v = b << 16; v < (b + 1) << 16; v++)
+			h += (uint64_t) fec_golay2412_decode_symbol(v) * ((uint64_t) v * 0x9E3779B97F4A7C15ull + 1u);
+		digest[b] = h;
 	}
 	return 0;
 }
