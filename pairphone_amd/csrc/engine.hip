@@ -1,8 +1,10 @@
 /*
  * engine.hip -- host side of the MI355X MELPe-1200 engine: the C ABI
  * (include/melpe.h drop-in, include/melpe_batch.h batched), device table
- * upload, and the small kernels (reset, init, parameter sharing, the
- * synthetic test-signal generator).
+ * upload, and the kernels that are not the codec's: reset, init, parameter
+ * sharing, the synthetic test-signal generator, voice crypt, the VAD, the
+ * VAD-framed stream format, the modem, the lane-order sort and the
+ * basic-op / helper evaluators of the parity tests.
  *
  * The codec kernels live in their own translation units, compiled in
  * parallel (pairphone_amd/build.py) and linked into libmelpe_amd.so:
@@ -18,6 +20,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <stdint.h>
+#include <initializer_list>
 #include <string>
 #include <mutex>
 #include <vector>
@@ -891,9 +894,9 @@ struct melpe_engine {
 	int channels = 0;
 	hipStream_t stream = nullptr;	/* the device's engine stream (g_dev_stream), shared */
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
-	hipEvent_t ev_in = nullptr, ev_out = nullptr;	/* EngineCall's hops to and from the engine stream */
+	hipEvent_t ev_in = nullptr, ev_out = nullptr;	/* engine_call's hops to and from the engine stream */
 	hipEvent_t ev_host = nullptr;	/* host_finish: the end of a host call's own work */
-	hipEvent_t ev_pin = nullptr, ev_npp = nullptr;	/* melpe_encode_pipe_dev's hops to / from the NPP stream */
+	hipEvent_t ev_pin = nullptr, ev_npp = nullptr;	/* pipe_step's hops to / from cin */
 	EncState *d_enc = nullptr;
 	DecState *d_dec = nullptr;
 	synth_state *d_syn = nullptr;
@@ -931,7 +934,7 @@ struct melpe_engine {
 		bool used = false;
 	} slot[2];
 	hipStream_t cin = nullptr, cout = nullptr;
-	/* melpe_duplex_pipe_dev's decoder stream and its hops */
+	/* pipe_step's decoder stream and its hop back */
 	hipStream_t cdec = nullptr;
 	hipEvent_t ev_dec = nullptr;
 	long async_calls = 0;
@@ -1115,26 +1118,33 @@ static int ensure_device_tables(int dev)
 	return 0;
 }
 
-static void ev_begin(melpe_engine *e, hipStream_t s)
-{
-	hipEventRecord(e->ev0, s);
-}
+/* what melpe_last_kernel_ms reports of a call: nothing (the previous timed
+ * call stands), resolved lazily when it is asked for, or waited for here */
+enum Timing { TIME_NONE, TIME_LAZY, TIME_SYNC };
 
-static void ev_end(melpe_engine *e, hipStream_t s, bool sync)
+/* runs `launches` (which enqueue on s) between the engine's two timing
+ * events; a failed launch leaves the previous timing */
+template <class F> static int timed(melpe_engine *e, hipStream_t s, Timing t, F &&launches)
 {
+	if (t == TIME_NONE)
+		return launches();
+	hipEventRecord(e->ev0, s);
+	if (int rc = launches())
+		return rc;
 	hipEventRecord(e->ev1, s);
-	if (sync) {
+	if (t == TIME_SYNC) {
 		hipEventSynchronize(e->ev1);
 		hipEventElapsedTime(&e->last_ms, e->ev0, e->ev1);
 	} else {
 		e->last_ms = -1.f;	/* resolved lazily in melpe_last_kernel_ms */
 	}
+	return 0;
 }
 
-/* after enqueueing this engine's work on stream s (EngineCall records it on
- * every exit of a call once the call has started enqueueing, error paths
- * included, so a later host-side wait also covers the work a failed call
- * left in flight).  A stream's event is reused; at most MAX_MARKS streams
+/* after enqueueing this engine's work on stream s (engine_call records it on
+ * every exit of a call, error paths included, so a later host-side wait also
+ * covers the work a failed call left in flight).  A stream's event is
+ * reused; at most MAX_MARKS streams
  * are tracked, beyond that the oldest mark is waited for and recycled. */
 #define MAX_MARKS 16
 static int engine_mark(melpe_engine *e, hipStream_t s)
@@ -1173,7 +1183,7 @@ static int engine_wait(melpe_engine *e)
  * holds the engine's lock for its whole body: it stages data through the
  * engine's shared buffers (d_mask, d_pcm, d_bits, d_npp), which another
  * thread's call on the same engine would otherwise overwrite or reallocate
- * under it.  (The lock is recursive: ENGINE_WAIT and EngineCall take it
+ * under it.  (The lock is recursive: ENGINE_WAIT and engine_call take it
  * again inside.) */
 #define HOST_LOCK(e) std::lock_guard<std::recursive_mutex> _host_lk((e)->mu)
 /* the host waits for the work this call enqueued on the engine stream (an
@@ -1185,51 +1195,272 @@ static int host_finish(melpe_engine *e)
 	return 0;
 }
 #define HOST_FINISH(e) do { if (int _r = host_finish(e)) return _r; } while (0)
-/* one *_dev call of an engine: holds the engine's lock (the host-side
- * bookkeeping -- marks, the lane-order buffers -- is shared by the calls of
- * every thread) and records the stream's mark when it ends */
-struct EngineCall {
-	melpe_engine *e;
-	hipStream_t user, run;
-	std::lock_guard<std::recursive_mutex> lk;
-	bool finished = false;
-	EngineCall(melpe_engine *e_, hipStream_t s_) : e(e_), user(s_), run(s_), lk(e_->mu)
-	{
-		/* the call's kernels run on the device's engine stream, ordered
-		 * after the caller's stream and before its later work (two event
-		 * hops).  The runtime holds kernel scratch per hardware queue; the
-		 * codec kernels' is reserved on the engine stream's queue at create
-		 * (engine_reserve), and a second queue running them would hold its
-		 * own -- at 14 GB per queue for the analysis kernels two queues
-		 * exceed the runtime's threshold and it reclaims one queue's
-		 * scratch to grant the other's, hundreds of ms per launch. */
-		if (s_ != e->stream && hipEventRecord(e->ev_in, s_) == hipSuccess &&
-		    hipStreamWaitEvent(e->stream, e->ev_in, 0) == hipSuccess)
-			run = e->stream;
+/*
+ * One *_dev call of an engine on the caller's stream `user`.  It holds the
+ * engine's lock (the host-side bookkeeping -- marks, the lane-order buffers
+ * -- is shared by the calls of every thread), runs `launches(s)` with the
+ * stream to enqueue on, timed as `t` asks, and records the caller's stream's
+ * mark on every exit, error exits included.
+ *
+ * The call's kernels run on the device's engine stream, ordered after the
+ * caller's stream and before its later work (two event hops).  The runtime
+ * holds kernel scratch per hardware queue; the codec kernels' is reserved on
+ * the engine stream's queue at create (engine_reserve), and a second queue
+ * running them would hold its own -- at 14 GB per queue for the analysis
+ * kernels two queues exceed the runtime's threshold and it reclaims one
+ * queue's scratch to grant the other's, hundreds of ms per launch.
+ *
+ * An entry point returns this call's result, so a failed hop back (the
+ * caller's later work would not be ordered after the kernels) is reported;
+ * after failed launches the hop and the mark are made all the same, and the
+ * launches' error stands.
+ */
+template <class F> static int engine_call(melpe_engine *e, hipStream_t user, Timing t, F &&launches)
+{
+	DEVGUARD(e->device);
+	std::lock_guard<std::recursive_mutex> lk(e->mu);
+	hipStream_t run = user;
+	if (user != e->stream && hipEventRecord(e->ev_in, user) == hipSuccess &&
+	    hipStreamWaitEvent(e->stream, e->ev_in, 0) == hipSuccess)
+		run = e->stream;
+	const int rc = timed(e, run, t, [&] { return launches(run); });
+	std::string err;
+	if (rc)
+		err = g_err;
+	hipError_t hop = hipSuccess;
+	if (run != user && (hop = hipEventRecord(e->ev_out, run)) == hipSuccess)
+		hop = hipStreamWaitEvent(user, e->ev_out, 0);
+	const int mark = engine_mark(e, user);
+	if (rc) {
+		g_err = err;
+		return rc;
 	}
-	/* the hop back to the caller's stream and the call's mark; an entry
-	 * point returns its result, so a failed hop (the caller's later work
-	 * would not be ordered after the kernels) is reported */
-	int finish()
-	{
-		finished = true;
-		if (run != user) {
-			HIPCHK(hipEventRecord(e->ev_out, run));
-			HIPCHK(hipStreamWaitEvent(user, e->ev_out, 0));
-		}
-		return engine_mark(e, user);
-	}
-	/* early error returns: the same steps, best effort */
-	~EngineCall()
-	{
-		if (finished)
-			return;
-		if (run != user && hipEventRecord(e->ev_out, run) == hipSuccess)
-			hipStreamWaitEvent(user, e->ev_out, 0);
-		engine_mark(e, user);
-	}
+	if (hop != hipSuccess)
+		return fail("the hop from the engine stream back to the caller's", hop);
+	return mark;
+}
+
+static const uint8_t *stage_mask(melpe_engine *e, const uint8_t *mask_host, int *rc)
+{
+	*rc = 0;
+	if (!mask_host)
+		return nullptr;
+	hipError_t er = hipMemcpyAsync(e->d_mask, mask_host, (size_t) e->channels,
+				       hipMemcpyHostToDevice, e->stream);
+	if (er != hipSuccess)
+		*rc = fail("hipMemcpyAsync(mask)", er);
+	return e->d_mask;
+}
+
+/* one buffer of a *_host call and its device staging.  XFER_IN_MASKED: up
+ * only when the call has a mask, so that inactive channels keep the caller's
+ * data when the buffer comes back down.  A null host pointer: no transfer. */
+enum { XFER_IN = 1, XFER_IN_MASKED = 2, XFER_OUT = 4 };
+struct Xfer {
+	const void *host;
+	void *dev;
+	size_t bytes;
+	int dir;
 };
-#define ENGINE_CALL(e, s) EngineCall _call(e, s); s = _call.run
+
+/* The engine's staged host call: under the engine's lock and after every
+ * call of the engine already enqueued, the mask and the uploads, then
+ * `launches(mask, s)` as one synchronously timed engine_call, the
+ * downloads, and the wait -- all on the engine stream, in list order. */
+template <class F>
+static int engine_host_call(melpe_engine *e, const uint8_t *active, std::initializer_list<Xfer> xs, F &&launches)
+{
+	DEVGUARD(e->device);
+	HOST_LOCK(e);
+	ENGINE_WAIT(e);
+	int rc;
+	const uint8_t *m = stage_mask(e, active, &rc);
+	if (rc)
+		return rc;
+	for (const Xfer &x : xs)
+		if (x.host && ((x.dir & XFER_IN) || ((x.dir & XFER_IN_MASKED) && active)))
+			HIPCHK(hipMemcpyAsync(x.dev, x.host, x.bytes, hipMemcpyHostToDevice, e->stream));
+	if ((rc = engine_call(e, e->stream, TIME_SYNC, [&](hipStream_t s) { return launches(m, s); })))
+		return rc;
+	for (const Xfer &x : xs)
+		if (x.host && (x.dir & XFER_OUT))
+			HIPCHK(hipMemcpyAsync((void *) x.host, x.dev, x.bytes, hipMemcpyDeviceToHost, e->stream));
+	return host_finish(e);
+}
+
+/* The engine-less staged host call (VAD, voice crypt, link): under the
+ * current device's stage mutex, xs[i].dev is carved from the device's stage
+ * buffer (each part rounded up to 4 bytes; null where the host pointer is),
+ * then the uploads, `dev_call()` on the null stream, and the downloads, with
+ * synchronous copies. */
+template <class F> static int stage_host_call(const char *who, Xfer *xs, int n, F &&dev_call)
+{
+	size_t total = 0;
+	for (int i = 0; i < n; i++)
+		total += (xs[i].bytes + 3) & ~(size_t) 3;
+	int dev = 0;
+	HIPCHK(hipGetDevice(&dev));
+	std::lock_guard<std::mutex> lk(g_stage[dev & 63].mu);
+	char *d = nullptr;
+	if (int r = stage_get(dev, total, (void **) &d))
+		return r;
+	for (int i = 0; i < n; i++) {
+		xs[i].dev = xs[i].host ? d : nullptr;
+		d += (xs[i].bytes + 3) & ~(size_t) 3;
+	}
+	hipError_t he;
+	for (int i = 0; i < n; i++)
+		if (xs[i].dev && (xs[i].dir & XFER_IN) &&
+		    (he = hipMemcpy(xs[i].dev, xs[i].host, xs[i].bytes, hipMemcpyHostToDevice)) != hipSuccess)
+			return fail((std::string(who) + ": upload").c_str(), he);
+	if (int rc = dev_call())
+		return rc;
+	for (int i = 0; i < n; i++)
+		if (xs[i].dev && (xs[i].dir & XFER_OUT) &&
+		    (he = hipMemcpy((void *) xs[i].host, xs[i].dev, xs[i].bytes, hipMemcpyDeviceToHost)) != hipSuccess)
+			return fail((std::string(who) + ": download").c_str(), he);
+	return 0;
+}
+
+/* the VAD, modem and link state records hold 32-bit words */
+static int state_aligned(const char *who, const void *d_state)
+{
+	if ((uintptr_t) d_state & 3)
+		return fail_msg(std::string(who) + ": state must be 4-byte aligned");
+	return 0;
+}
+
+static int vad_launch(void *d_state, const void *d_sp, void *d_votes, void *d_gate, const void *d_active,
+		      int channels, hipStream_t s)
+{
+	k_vad<<<grid_for(channels), WAVE, 0, s>>>((VadState *) d_state, (const int16_t *) d_sp, (uint8_t *) d_votes,
+						  (uint8_t *) d_gate, (const uint8_t *) d_active, channels);
+	HIPCHK(hipGetLastError());
+	return 0;
+}
+
+/*
+ * The engine's side streams, made at the first call that needs them: cout
+ * and cin (the host-fed pipeline's copies; the pipelined calls' NPP and VAD
+ * run on cin) and, with `dec`, cdec (melpe_duplex_pipe_dev's decode) and its
+ * event.  The runtime spreads streams over the process's hardware queues in
+ * the order they are made, so they are made in one place: cout, cin, then
+ * cdec.  Each queue's scratch is reserved here as engine_warm does on the
+ * engine stream's: the NPP kernel's on cin (only that kernel and the VAD run
+ * there besides copies), the decoder kernels' on cdec.
+ *
+ * All of it under the engine's lock, into locals: the engine's fields are
+ * assigned only once every warm-up has run and been waited for, so no call
+ * of another thread ever sees a stream whose queue has no scratch yet, and a
+ * failure leaves the engine as it was.
+ */
+static int engine_streams(melpe_engine *e, bool dec)
+{
+	std::lock_guard<std::recursive_mutex> lk(e->mu);
+	const bool side = !e->cin;
+	dec = dec && !e->cdec;
+	if (!side && !dec)
+		return 0;
+	DEVGUARD(e->device);
+	hipStream_t cout = nullptr, cin = nullptr, cdec = nullptr;
+	hipEvent_t ev_dec = nullptr;
+	hipError_t er = hipSuccess;
+	const char *what = nullptr;
+#define STREAM_STEP(expr) if (er == hipSuccess && (er = (hipError_t) (expr)) != hipSuccess) what = #expr
+	if (side) {
+		STREAM_STEP(hipStreamCreateWithFlags(&cout, hipStreamNonBlocking));
+		STREAM_STEP(hipStreamCreateWithFlags(&cin, hipStreamNonBlocking));
+		STREAM_STEP(kl_npp_warm(e->channels, cin));
+		STREAM_STEP(hipStreamSynchronize(cin));
+	}
+	if (dec) {
+		STREAM_STEP(hipEventCreateWithFlags(&ev_dec, hipEventDisableTiming));
+		STREAM_STEP(hipStreamCreateWithFlags(&cdec, hipStreamNonBlocking));
+		STREAM_STEP(kl_dec_warm(e->channels, cdec));
+		if (e->d_hb)
+			STREAM_STEP(kl_dec2_warm(e->channels, cdec));
+		STREAM_STEP(hipStreamSynchronize(cdec));
+	}
+#undef STREAM_STEP
+	if (er != hipSuccess) {
+		for (hipStream_t s : {cout, cin, cdec})
+			if (s)
+				hipStreamDestroy(s);
+		if (ev_dec)
+			hipEventDestroy(ev_dec);
+		return fail(what, er);
+	}
+	if (side) {
+		e->cout = cout;
+		e->cin = cin;
+	}
+	if (dec) {
+		e->ev_dec = ev_dec;
+		e->cdec = cdec;
+	}
+	return 0;
+}
+
+/*
+ * The pipelined step behind melpe_encode_pipe_dev, melpe_duplex_pipe_dev and
+ * melpe_tx_pipe_dev, on three queues: this superframe's analysis on the
+ * engine stream, and once its lane-order sort is done (ev_pin: after the
+ * caller's work too, which the engine stream waited for, and so that the
+ * analysis' waves, the longest, are dispatched first and the others fill the
+ * slots they free) the decode on cdec and the next superframe's VAD and NPP
+ * on cin.  The NPP touches only the records' NppState and the next PCM, the
+ * analysis only their EncAna and this PCM, the VAD its own state; the
+ * encoder and decoder halves of a record and their lane-order buffers
+ * (bin_enc, bin_dec) are disjoint.  The hop back to the caller covers all
+ * three; melpe_last_kernel_ms reports the analysis.
+ */
+struct PipeNext {	/* the next superframe, or none */
+	void *sp;
+	const void *mask;	/* the NPP's mask: with a VAD the gate it writes */
+	void *vad, *votes;	/* the VAD to run first (or null): its state and votes */
+	const void *active;	/* the VAD's mask */
+};
+struct PipeDec {	/* a decode, or none */
+	void *sp;
+	const void *bits, *active;
+};
+
+static int pipe_step(melpe_engine *e, void *d_bits, const void *d_sp, const void *d_active, const PipeNext *nx,
+		     const PipeDec *dc, hipStream_t user)
+{
+	if (nx || dc)
+		if (int rc = engine_streams(e, dc != nullptr))
+			return rc;
+	return engine_call(e, user, TIME_NONE, [&](hipStream_t s) {
+		const int rc = timed(e, s, TIME_LAZY, [&] {
+			HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits,
+						       (const uint8_t *) d_active, s, (nx || dc) ? e->ev_pin : nullptr));
+			return 0;
+		});
+		if (rc)
+			return rc;
+		if (dc) {
+			HIPCHK(hipStreamWaitEvent(e->cdec, e->ev_pin, 0));
+			HIPCHK((hipError_t) dec_launch(e, (int16_t *) dc->sp, (const uint8_t *) dc->bits,
+						       (const uint8_t *) dc->active, e->cdec));
+			HIPCHK(hipEventRecord(e->ev_dec, e->cdec));
+		}
+		if (nx) {
+			HIPCHK(hipStreamWaitEvent(e->cin, e->ev_pin, 0));
+			if (nx->vad)
+				if (int r = vad_launch(nx->vad, nx->sp, nx->votes, (void *) nx->mask, nx->active,
+						       e->channels, e->cin))
+					return r;
+			HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) nx->sp, (const uint8_t *) nx->mask,
+						       e->channels, e->cin));
+			HIPCHK(hipEventRecord(e->ev_npp, e->cin));
+			HIPCHK(hipStreamWaitEvent(s, e->ev_npp, 0));
+		}
+		if (dc)
+			HIPCHK(hipStreamWaitEvent(s, e->ev_dec, 0));
+		return 0;
+	});
+}
 
 extern "C" {
 
@@ -1250,10 +1481,8 @@ const char *melpe_last_error(void)
  *   no live channel (every lane exits at once), and waited for.  (Scratch
  *   is held per hardware queue: a caller's own stream may map to another
  *   queue, whose first dispatch reserves it again.)
+ * engine_warm is the second half, engine_reserve the first and then both.
  */
-/* every codec kernel dispatched once on the engine's stream with the grid
- * of a real launch and no live channel, and waited for: the runtime sizes
- * that hardware queue's scratch by the dispatches it sees */
 static int engine_warm(melpe_engine *e)
 {
 	hipError_t er;
@@ -1418,6 +1647,7 @@ int melpe_engine_set_lane_order(melpe_engine *e, int on)
 {
 	if (!e)
 		return fail_msg("melpe_engine_set_lane_order: null engine");
+	std::lock_guard<std::recursive_mutex> lk(e->mu);
 	e->lane_order = on ? 1 : 0;
 	return 0;
 }
@@ -1458,6 +1688,7 @@ int melpe_engine_set_ana_waves(melpe_engine *e, int waves)
 {
 	if (!e || !(waves == 0 || waves == 1 || waves == 4))
 		return fail_msg("melpe_engine_set_ana_waves: waves must be 0 (auto), 1 or 4");
+	std::lock_guard<std::recursive_mutex> lk(e->mu);
 	e->ana_waves = waves;
 	return 0;
 }
@@ -1528,29 +1759,16 @@ int melpe_engine_channels(const melpe_engine *e)
 	return e ? e->channels : 0;
 }
 
-static const uint8_t *stage_mask(melpe_engine *e, const uint8_t *mask_host, int *rc)
-{
-	*rc = 0;
-	if (!mask_host)
-		return nullptr;
-	hipError_t er = hipMemcpyAsync(e->d_mask, mask_host, (size_t) e->channels,
-				       hipMemcpyHostToDevice, e->stream);
-	if (er != hipSuccess)
-		*rc = fail("hipMemcpyAsync(mask)", er);
-	return e->d_mask;
-}
-
 int melpe_engine_reset_dev(melpe_engine *e, const void *d_mask, int which, void *hip_stream)
 {
 	if (!e || which < 1 || which > 3)
 		return fail_msg("melpe_engine_reset_dev: bad arguments");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	k_reset<<<grid_for(e->channels), WAVE, 0, s>>>(
-		e->d_enc, e->d_dec, (const uint8_t *) d_mask, e->channels, which);
-	HIPCHK(hipGetLastError());
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
+		k_reset<<<grid_for(e->channels), WAVE, 0, s>>>(
+			e->d_enc, e->d_dec, (const uint8_t *) d_mask, e->channels, which);
+		HIPCHK(hipGetLastError());
+		return 0;
+	});
 }
 
 int melpe_engine_reset(melpe_engine *e, const uint8_t *mask_host, int which)
@@ -1573,17 +1791,12 @@ int melpe_engine_reset(melpe_engine *e, const uint8_t *mask_host, int which)
 	return 0;
 }
 
-static int npp_launch(melpe_engine *e, int16_t *d_sp, int frames, int stride,
-		      const uint8_t *d_act, hipStream_t s, bool sync, int rate1200)
+/* melpe_npp_dev / melpe_npp_host / melpe_n: `frames` frames per channel at `stride` samples */
+static int npp_args_ok(int frames, int stride)
 {
 	if (frames <= 0 || stride < frames * MELPE_FRAME_SAMPLES)
 		return fail_msg("melpe_npp: bad frames/stride");
-	DEVGUARD(e->device);
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) kl_npp(e->d_enc, d_sp, frames, stride, d_act, e->channels, rate1200, s));
-	ev_end(e, s, sync);
-	return _call.finish();
+	return 0;
 }
 
 int melpe_npp_dev(melpe_engine *e, void *d_sp, int frames, int stride, const void *d_active,
@@ -1591,18 +1804,27 @@ int melpe_npp_dev(melpe_engine *e, void *d_sp, int frames, int stride, const voi
 {
 	if (!e || !d_sp)
 		return fail_msg("melpe_npp_dev: null argument");
-	return npp_launch(e, (int16_t *) d_sp, frames, stride, (const uint8_t *) d_active,
-			  (hipStream_t) hip_stream, false, 1);
+	if (int rc = npp_args_ok(frames, stride))
+		return rc;
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		HIPCHK((hipError_t) kl_npp(e->d_enc, (int16_t *) d_sp, frames, stride, (const uint8_t *) d_active,
+					   e->channels, 1, s));
+		return 0;
+	});
 }
 
 int melpe_npp_host(melpe_engine *e, int16_t *sp, int frames, int stride, const uint8_t *active)
 {
 	if (!e || !sp || stride <= 0)
 		return fail_msg("melpe_npp_host: bad arguments");
+	if (int rc = npp_args_ok(frames, stride))
+		return rc;
 	DEVGUARD(e->device);
 	HOST_LOCK(e);
+	/* the staging buffer is grown before the staged call, under the same
+	 * lock and once nothing enqueued reads the old one any more */
 	ENGINE_WAIT(e);
-	size_t bytes = sizeof(int16_t) * (size_t) stride * e->channels;
+	const size_t bytes = sizeof(int16_t) * (size_t) stride * e->channels;
 	if (e->npp_bytes < bytes) {
 		HIPCHK(hipFree(e->d_npp));
 		e->d_npp = nullptr;
@@ -1610,36 +1832,19 @@ int melpe_npp_host(melpe_engine *e, int16_t *sp, int frames, int stride, const u
 		HIPCHK(hipMalloc(&e->d_npp, bytes));
 		e->npp_bytes = bytes;
 	}
-	int16_t *d = e->d_npp;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (!rc) {
-		hipError_t ec = hipMemcpyAsync(d, sp, bytes, hipMemcpyHostToDevice, e->stream);
-		rc = ec == hipSuccess ? npp_launch(e, d, frames, stride, m, e->stream, true, 1)
-				      : fail("npp copy in", ec);
-		if (!rc) {
-			hipError_t er = hipMemcpyAsync(sp, d, bytes, hipMemcpyDeviceToHost, e->stream);
-			if (er == hipSuccess)
-				er = hipEventRecord(e->ev_host, e->stream);
-			if (er == hipSuccess)
-				er = hipEventSynchronize(e->ev_host);
-			if (er != hipSuccess)
-				rc = fail("npp copy back", er);
-		}
-	}
-	return rc;
+	return engine_host_call(e, active, {{sp, e->d_npp, bytes, XFER_IN | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) {
+		HIPCHK((hipError_t) kl_npp(e->d_enc, e->d_npp, frames, stride, m, e->channels, 1, s));
+		return 0;
+	});
 }
 
-static int encode_launch(melpe_engine *e, unsigned char *d_bits, int16_t *d_sp,
-			 const uint8_t *d_act, hipStream_t s, bool sync)
+/* melpe_a of every channel: the NPP in place, then the analysis */
+static int encode_kernels(melpe_engine *e, void *d_bits, void *d_sp, const void *d_act, hipStream_t s)
 {
-	DEVGUARD(e->device);
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) kl_enc_npp(e->d_enc, d_sp, d_act, e->channels, s));
-	HIPCHK((hipError_t) ana_launch(e, d_sp, d_bits, d_act, s));
-	ev_end(e, s, sync);
-	return _call.finish();
+	HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp, (const uint8_t *) d_act, e->channels, s));
+	HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits, (const uint8_t *) d_act, s));
+	return 0;
 }
 
 int melpe_encode_dev(melpe_engine *e, void *d_bits, void *d_sp, const void *d_active,
@@ -1647,20 +1852,19 @@ int melpe_encode_dev(melpe_engine *e, void *d_bits, void *d_sp, const void *d_ac
 {
 	if (!e || !d_bits || !d_sp)
 		return fail_msg("melpe_encode_dev: null argument");
-	return encode_launch(e, (unsigned char *) d_bits, (int16_t *) d_sp,
-			     (const uint8_t *) d_active, (hipStream_t) hip_stream, false);
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY,
+			   [&](hipStream_t s) { return encode_kernels(e, d_bits, d_sp, d_active, s); });
 }
 
 int melpe_encode_npp_dev(melpe_engine *e, void *d_sp, const void *d_active, void *hip_stream)
 {
 	if (!e || !d_sp)
 		return fail_msg("melpe_encode_npp_dev: null argument");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp, (const uint8_t *) d_active,
-				       e->channels, s));
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
+		HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp, (const uint8_t *) d_active,
+					       e->channels, s));
+		return 0;
+	});
 }
 
 int melpe_encode_ana_dev(melpe_engine *e, void *d_bits, const void *d_sp, const void *d_active,
@@ -1668,15 +1872,12 @@ int melpe_encode_ana_dev(melpe_engine *e, void *d_bits, const void *d_sp, const 
 {
 	if (!e || !d_bits || !d_sp)
 		return fail_msg("melpe_encode_ana_dev: null argument");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits,
-				       (const uint8_t *) d_active, s));
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
+		HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits,
+					       (const uint8_t *) d_active, s));
+		return 0;
+	});
 }
-
-static int side_streams(melpe_engine *e);
 
 int melpe_encode_pipe_dev(melpe_engine *e, void *d_bits, const void *d_sp, const void *d_active,
 			  void *d_sp_next, const void *d_active_next, void *hip_stream)
@@ -1685,35 +1886,9 @@ int melpe_encode_pipe_dev(melpe_engine *e, void *d_bits, const void *d_sp, const
 		return fail_msg("melpe_encode_pipe_dev: null argument");
 	if (d_sp_next == d_sp)
 		return fail_msg("melpe_encode_pipe_dev: the next superframe's PCM must be another buffer");
-	DEVGUARD(e->device);
-	if (d_sp_next)
-		if (int rc = side_streams(e))
-			return rc;
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	/* the analysis on the engine stream; the next superframe's NPP on the
-	 * engine's cin stream once the analysis' lane-order sort is done (after the
-	 * caller's work, too, which the engine stream waited for).  The NPP
-	 * touches only the records' NppState and d_sp_next, the analysis only
-	 * their EncAna and d_sp. */
-	ev_begin(e, s);
-	HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits, (const uint8_t *) d_active,
-				       s, d_sp_next ? e->ev_pin : nullptr));
-	ev_end(e, s, false);
-	if (d_sp_next) {
-		const hipStream_t ns = e->cin;
-		HIPCHK(hipStreamWaitEvent(ns, e->ev_pin, 0));
-		HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp_next, (const uint8_t *) d_active_next,
-					       e->channels, ns));
-		HIPCHK(hipEventRecord(e->ev_npp, ns));
-	}
-	/* the hop back to the caller covers the NPP too */
-	if (d_sp_next)
-		HIPCHK(hipStreamWaitEvent(s, e->ev_npp, 0));
-	return _call.finish();
+	const PipeNext nx = {d_sp_next, d_active_next, nullptr, nullptr, nullptr};
+	return pipe_step(e, d_bits, d_sp, d_active, d_sp_next ? &nx : nullptr, nullptr, (hipStream_t) hip_stream);
 }
-
-static int dec_queue(melpe_engine *e);
 
 int melpe_duplex_pipe_dev(melpe_engine *e, void *d_bits, const void *d_sp, const void *d_active,
 			  void *d_sp_next, const void *d_active_next, void *d_dec_sp,
@@ -1725,108 +1900,27 @@ int melpe_duplex_pipe_dev(melpe_engine *e, void *d_bits, const void *d_sp, const
 		return fail_msg("melpe_duplex_pipe_dev: the next superframe's PCM must be another buffer");
 	if (d_dec_bits && (d_dec_bits == d_bits || d_dec_sp == d_sp || d_dec_sp == d_sp_next))
 		return fail_msg("melpe_duplex_pipe_dev: the decode's buffers must differ from the encode's");
-	DEVGUARD(e->device);
-	if (d_sp_next || d_dec_bits)
-		if (int rc = d_dec_bits ? dec_queue(e) : side_streams(e))
-			return rc;
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	/* three queues: the analysis of this superframe on the engine stream, and
-	 * once its lane-order sort is done (so that the analysis' waves, the
-	 * longest, are dispatched first) the next superframe's NPP on cin
-	 * (melpe_encode_pipe_dev) and the decode on cdec.  The encoder and
-	 * decoder halves of a record and their lane-order buffers (bin_enc,
-	 * bin_dec) are disjoint. */
-	ev_begin(e, s);
-	HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits, (const uint8_t *) d_active,
-				       s, (d_sp_next || d_dec_bits) ? e->ev_pin : nullptr));
-	ev_end(e, s, false);
-	if (d_dec_bits) {
-		HIPCHK(hipStreamWaitEvent(e->cdec, e->ev_pin, 0));
-		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_dec_sp, (const uint8_t *) d_dec_bits,
-					       (const uint8_t *) d_dec_active, e->cdec));
-		HIPCHK(hipEventRecord(e->ev_dec, e->cdec));
-	}
-	if (d_sp_next) {
-		HIPCHK(hipStreamWaitEvent(e->cin, e->ev_pin, 0));
-		HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp_next, (const uint8_t *) d_active_next,
-					       e->channels, e->cin));
-		HIPCHK(hipEventRecord(e->ev_npp, e->cin));
-		HIPCHK(hipStreamWaitEvent(s, e->ev_npp, 0));
-	}
-	/* the hop back to the caller covers the decode too */
-	if (d_dec_bits)
-		HIPCHK(hipStreamWaitEvent(s, e->ev_dec, 0));
-	return _call.finish();
+	const PipeNext nx = {d_sp_next, d_active_next, nullptr, nullptr, nullptr};
+	const PipeDec dc = {d_dec_sp, d_dec_bits, d_dec_active};
+	return pipe_step(e, d_bits, d_sp, d_active, d_sp_next ? &nx : nullptr, d_dec_bits ? &dc : nullptr,
+			 (hipStream_t) hip_stream);
 }
 
 int melpe_encode_host(melpe_engine *e, unsigned char *bits, int16_t *sp, const uint8_t *active)
 {
 	if (!e || !bits || !sp)
 		return fail_msg("melpe_encode_host: null argument");
-	DEVGUARD(e->device);
-	HOST_LOCK(e);
-	ENGINE_WAIT(e);
-	size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels;
-	size_t bb = (size_t) 11 * e->channels;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(e->d_pcm, sp, pb, hipMemcpyHostToDevice, e->stream));
-	if (active)	/* inactive channels keep the caller's bits */
-		HIPCHK(hipMemcpyAsync(e->d_bits, bits, bb, hipMemcpyHostToDevice, e->stream));
-	rc = encode_launch(e, e->d_bits, e->d_pcm, m, e->stream, true);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(sp, e->d_pcm, pb, hipMemcpyDeviceToHost, e->stream));
-	HIPCHK(hipMemcpyAsync(bits, e->d_bits, bb, hipMemcpyDeviceToHost, e->stream));
-	HOST_FINISH(e);
-	return 0;
+	const size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels, bb = (size_t) 11 * e->channels;
+	return engine_host_call(e, active,
+				{{sp, e->d_pcm, pb, XFER_IN | XFER_OUT}, {bits, e->d_bits, bb, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) { return encode_kernels(e, e->d_bits, e->d_pcm, m, s); });
 }
 
-/* The engine's two side streams, made at the first call that needs them
- * (the host-fed pipeline's copies; the pipelined encode's NPP runs on cin).
- * The runtime spreads streams over the process's hardware queues in the
- * order they are made, so they are made in one place, cout then cin.  The
- * NPP kernel's scratch is reserved on cin's queue here (only that kernel
- * runs there besides copies). */
-static int side_streams(melpe_engine *e)
-{
-	if (e->cin)
-		return 0;
-	HIPCHK(hipStreamCreateWithFlags(&e->cout, hipStreamNonBlocking));
-	HIPCHK(hipStreamCreateWithFlags(&e->cin, hipStreamNonBlocking));
-	HIPCHK((hipError_t) kl_npp_warm(e->channels, e->cin));
-	HIPCHK(hipStreamSynchronize(e->cin));
-	return 0;
-}
-
-/* melpe_duplex_pipe_dev's decoder stream, made after the two side streams
- * (so the three land on hardware queues in a fixed order), with the
- * decoder kernels' scratch reserved on its queue as engine_warm does on the
- * engine stream's */
-static int dec_queue(melpe_engine *e)
-{
-	if (e->cdec)
-		return 0;
-	if (int rc = side_streams(e))
-		return rc;
-	if (!e->ev_dec)
-		HIPCHK(hipEventCreateWithFlags(&e->ev_dec, hipEventDisableTiming));
-	HIPCHK(hipStreamCreateWithFlags(&e->cdec, hipStreamNonBlocking));
-	HIPCHK((hipError_t) kl_dec_warm(e->channels, e->cdec));
-	if (e->d_hb)
-		HIPCHK((hipError_t) kl_dec2_warm(e->channels, e->cdec));
-	HIPCHK(hipStreamSynchronize(e->cdec));
-	return 0;
-}
-
-/* the host-fed pipeline's buffers, made at its first call */
+/* the host-fed pipeline's buffers and streams, made at its first call */
 static int async_setup(melpe_engine *e)
 {
 	if (e->slot[0].pcm)
-		return 0;
+		return engine_streams(e, false);
 	const size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels, bb = (size_t) 11 * e->channels;
 	for (auto &sl : e->slot) {
 		HIPCHK(hipMalloc(&sl.pcm, pb));
@@ -1835,7 +1929,7 @@ static int async_setup(melpe_engine *e)
 		for (hipEvent_t *ev : {&sl.loaded, &sl.done, &sl.freed})
 			HIPCHK(hipEventCreateWithFlags(ev, hipEventDisableTiming));
 	}
-	return side_streams(e);
+	return engine_streams(e, false);
 }
 
 int melpe_encode_host_async(melpe_engine *e, unsigned char *bits, int16_t *sp, const uint8_t *active)
@@ -1888,24 +1982,16 @@ int melpe_encode_host_wait(melpe_engine *e)
 	return 0;
 }
 
-static int decode_launch(melpe_engine *e, int16_t *d_sp, const unsigned char *d_bits,
-			 const uint8_t *d_act, hipStream_t s, bool sync)
-{
-	DEVGUARD(e->device);
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) dec_launch(e, d_sp, d_bits, d_act, s));
-	ev_end(e, s, sync);
-	return _call.finish();
-}
-
 int melpe_decode_dev(melpe_engine *e, void *d_sp, const void *d_bits, const void *d_active,
 		     void *hip_stream)
 {
 	if (!e || !d_sp || !d_bits)
 		return fail_msg("melpe_decode_dev: null argument");
-	return decode_launch(e, (int16_t *) d_sp, (const unsigned char *) d_bits,
-			     (const uint8_t *) d_active, (hipStream_t) hip_stream, false);
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
+					       (const uint8_t *) d_active, s));
+		return 0;
+	});
 }
 
 int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
@@ -1913,24 +1999,13 @@ int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
 {
 	if (!e || !bits || !sp)
 		return fail_msg("melpe_decode_host: null argument");
-	DEVGUARD(e->device);
-	HOST_LOCK(e);
-	ENGINE_WAIT(e);
-	size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels;
-	size_t bb = (size_t) 11 * e->channels;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(e->d_bits, bits, bb, hipMemcpyHostToDevice, e->stream));
-	if (active)	/* inactive channels keep the caller's samples */
-		HIPCHK(hipMemcpyAsync(e->d_pcm, sp, pb, hipMemcpyHostToDevice, e->stream));
-	rc = decode_launch(e, e->d_pcm, e->d_bits, m, e->stream, true);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(sp, e->d_pcm, pb, hipMemcpyDeviceToHost, e->stream));
-	HOST_FINISH(e);
-	return 0;
+	const size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels, bb = (size_t) 11 * e->channels;
+	return engine_host_call(e, active,
+				{{bits, e->d_bits, bb, XFER_IN}, {sp, e->d_pcm, pb, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) {
+		HIPCHK((hipError_t) dec_launch(e, e->d_pcm, e->d_bits, m, s));
+		return 0;
+	});
 }
 
 /* The codec parameters as tensors (k_par.hip): the tap on the records of the
@@ -1939,14 +2014,10 @@ int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
 #define PAR_ROW_BYTES (sizeof(int16_t) * MELPE_PAR_WORDS * NF)
 #define QPAR_ROW_BYTES (sizeof(int16_t) * MELPE_QPAR_WORDS)
 
-static int params_launch(melpe_engine *e, int which, void *d_par, void *d_qpar, const unsigned char *d_bits,
-			 const uint8_t *d_act, hipStream_t s, bool sync)
+static int params_kernels(melpe_engine *e, int which, void *d_par, void *d_qpar, const void *d_bits,
+			  const void *d_active, hipStream_t s)
 {
-	if (((uintptr_t) d_par | (uintptr_t) d_qpar) & 3)
-		return fail_msg("melpe parameter rows: device buffers must be 4-byte aligned");
-	DEVGUARD(e->device);
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
+	const uint8_t *d_act = (const uint8_t *) d_active;
 	if (which == 0)
 		HIPCHK((hipError_t) kl_par_tap(e->d_enc, sizeof(EncState), offsetof(EncState, a) + offsetof(EncAna, par),
 					       d_par, d_qpar, d_act, e->channels, s));
@@ -1954,9 +2025,18 @@ static int params_launch(melpe_engine *e, int which, void *d_par, void *d_qpar, 
 		HIPCHK((hipError_t) kl_par_tap(e->d_dec, sizeof(DecState), offsetof(DecState, par), d_par, nullptr,
 					       d_act, e->channels, s));
 	else
-		HIPCHK((hipError_t) kl_parse(e->d_dec, d_par, d_bits, d_act, e->channels, s));
-	ev_end(e, s, sync);
-	return _call.finish();
+		HIPCHK((hipError_t) kl_parse(e->d_dec, d_par, (const uint8_t *) d_bits, d_act, e->channels, s));
+	return 0;
+}
+
+static int params_dev(melpe_engine *e, int which, void *d_par, void *d_qpar, const void *d_bits,
+		      const void *d_active, void *hip_stream)
+{
+	if (((uintptr_t) d_par | (uintptr_t) d_qpar) & 3)
+		return fail_msg("melpe parameter rows: device buffers must be 4-byte aligned");
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		return params_kernels(e, which, d_par, d_qpar, d_bits, d_active, s);
+	});
 }
 
 int melpe_encode_params_dev(melpe_engine *e, void *d_par, void *d_qpar, const void *d_active,
@@ -1964,16 +2044,14 @@ int melpe_encode_params_dev(melpe_engine *e, void *d_par, void *d_qpar, const vo
 {
 	if (!e || !d_par)
 		return fail_msg("melpe_encode_params_dev: null argument");
-	return params_launch(e, 0, d_par, d_qpar, nullptr, (const uint8_t *) d_active, (hipStream_t) hip_stream,
-			     false);
+	return params_dev(e, 0, d_par, d_qpar, nullptr, d_active, hip_stream);
 }
 
 int melpe_decode_params_dev(melpe_engine *e, void *d_par, const void *d_active, void *hip_stream)
 {
 	if (!e || !d_par)
 		return fail_msg("melpe_decode_params_dev: null argument");
-	return params_launch(e, 1, d_par, nullptr, nullptr, (const uint8_t *) d_active, (hipStream_t) hip_stream,
-			     false);
+	return params_dev(e, 1, d_par, nullptr, nullptr, d_active, hip_stream);
 }
 
 int melpe_parse_dev(melpe_engine *e, void *d_par, const void *d_bits, const void *d_active,
@@ -1981,8 +2059,7 @@ int melpe_parse_dev(melpe_engine *e, void *d_par, const void *d_bits, const void
 {
 	if (!e || !d_par || !d_bits)
 		return fail_msg("melpe_parse_dev: null argument");
-	return params_launch(e, 2, d_par, nullptr, (const unsigned char *) d_bits, (const uint8_t *) d_active,
-			     (hipStream_t) hip_stream, false);
+	return params_dev(e, 2, d_par, nullptr, d_bits, d_active, hip_stream);
 }
 
 /* the host forms stage the rows in d_pcm (C x 1,080 bytes: a channel's par
@@ -1990,32 +2067,17 @@ int melpe_parse_dev(melpe_engine *e, void *d_par, const void *d_bits, const void
 static int params_host(melpe_engine *e, int which, int16_t *par, int16_t *qpar, const unsigned char *bits,
 		       const uint8_t *active)
 {
-	DEVGUARD(e->device);
-	HOST_LOCK(e);
-	ENGINE_WAIT(e);
 	static_assert(PAR_ROW_BYTES + QPAR_ROW_BYTES <= sizeof(int16_t) * MELPE_SF_SAMPLES && PAR_ROW_BYTES % 4 == 0,
 		      "the rows fit the PCM staging buffer");
 	const size_t pb = PAR_ROW_BYTES * (size_t) e->channels, qb = QPAR_ROW_BYTES * (size_t) e->channels;
 	char *d_par = (char *) e->d_pcm, *d_qpar = qpar ? d_par + pb : nullptr;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (rc)
-		return rc;
-	if (bits)
-		HIPCHK(hipMemcpyAsync(e->d_bits, bits, (size_t) 11 * e->channels, hipMemcpyHostToDevice, e->stream));
-	if (active) {	/* inactive channels keep the caller's rows */
-		HIPCHK(hipMemcpyAsync(d_par, par, pb, hipMemcpyHostToDevice, e->stream));
-		if (qpar)
-			HIPCHK(hipMemcpyAsync(d_qpar, qpar, qb, hipMemcpyHostToDevice, e->stream));
-	}
-	rc = params_launch(e, which, d_par, d_qpar, e->d_bits, m, e->stream, true);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(par, d_par, pb, hipMemcpyDeviceToHost, e->stream));
-	if (qpar)
-		HIPCHK(hipMemcpyAsync(qpar, d_qpar, qb, hipMemcpyDeviceToHost, e->stream));
-	HOST_FINISH(e);
-	return 0;
+	return engine_host_call(e, active,
+				{{bits, e->d_bits, (size_t) 11 * e->channels, XFER_IN},
+				 {par, d_par, pb, XFER_IN_MASKED | XFER_OUT},
+				 {qpar, d_qpar, qb, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) {
+		return params_kernels(e, which, d_par, d_qpar, e->d_bits, m, s);
+	});
 }
 
 int melpe_encode_params_host(melpe_engine *e, int16_t *par, int16_t *qpar, const uint8_t *active)
@@ -2042,16 +2104,20 @@ int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits, c
 /* 2400 bps mode (codec2400.h): NPP of one 180-sample frame at RATE2400
  * (k_npp, melpe/npp.c:180-184 first-call branch), then analysis + 54-bit
  * packing (k_enc24); decode = channel read + synthesis of one frame */
-static int encode24_launch(melpe_engine *e, unsigned char *d_bits, int16_t *d_sp,
-			   const uint8_t *d_act, hipStream_t s, bool sync)
+static int encode24_kernels(melpe_engine *e, void *d_bits, void *d_sp, const void *d_act, hipStream_t s)
 {
-	DEVGUARD(e->device);
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) kl_npp(e->d_enc, d_sp, 1, MELPE_FRAME_SAMPLES, d_act, e->channels, 0, s));
-	HIPCHK((hipError_t) kl_enc24(e->d_enc, d_sp, d_bits, d_act, e->channels, s));
-	ev_end(e, s, sync);
-	return _call.finish();
+	HIPCHK((hipError_t) kl_npp(e->d_enc, (int16_t *) d_sp, 1, MELPE_FRAME_SAMPLES, (const uint8_t *) d_act,
+				   e->channels, 0, s));
+	HIPCHK((hipError_t) kl_enc24(e->d_enc, (const int16_t *) d_sp, (uint8_t *) d_bits, (const uint8_t *) d_act,
+				     e->channels, s));
+	return 0;
+}
+
+static int decode24_kernels(melpe_engine *e, void *d_sp, const void *d_bits, const void *d_act, hipStream_t s)
+{
+	HIPCHK((hipError_t) kl_dec24(e->d_dec, (int16_t *) d_sp, (const uint8_t *) d_bits, (const uint8_t *) d_act,
+				     e->channels, s));
+	return 0;
 }
 
 int melpe_encode2400_dev(melpe_engine *e, void *d_bits, void *d_sp, const void *d_active,
@@ -2059,8 +2125,8 @@ int melpe_encode2400_dev(melpe_engine *e, void *d_bits, void *d_sp, const void *
 {
 	if (!e || !d_bits || !d_sp)
 		return fail_msg("melpe_encode2400_dev: null argument");
-	return encode24_launch(e, (unsigned char *) d_bits, (int16_t *) d_sp,
-			       (const uint8_t *) d_active, (hipStream_t) hip_stream, false);
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY,
+			   [&](hipStream_t s) { return encode24_kernels(e, d_bits, d_sp, d_active, s); });
 }
 
 int melpe_decode2400_dev(melpe_engine *e, void *d_sp, const void *d_bits, const void *d_active,
@@ -2068,39 +2134,19 @@ int melpe_decode2400_dev(melpe_engine *e, void *d_sp, const void *d_bits, const 
 {
 	if (!e || !d_sp || !d_bits)
 		return fail_msg("melpe_decode2400_dev: null argument");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) kl_dec24(e->d_dec, (int16_t *) d_sp, (const uint8_t *) d_bits,
-				     (const uint8_t *) d_active, e->channels, s));
-	ev_end(e, s, false);
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY,
+			   [&](hipStream_t s) { return decode24_kernels(e, d_sp, d_bits, d_active, s); });
 }
 
 int melpe_encode2400_host(melpe_engine *e, unsigned char *bits, int16_t *sp, const uint8_t *active)
 {
 	if (!e || !bits || !sp)
 		return fail_msg("melpe_encode2400_host: null argument");
-	DEVGUARD(e->device);
-	HOST_LOCK(e);
-	ENGINE_WAIT(e);
-	size_t pb = sizeof(int16_t) * MELPE_FRAME_SAMPLES * (size_t) e->channels;
-	size_t bb = (size_t) MELPE_R24_BYTES * e->channels;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(e->d_pcm, sp, pb, hipMemcpyHostToDevice, e->stream));
-	if (active)
-		HIPCHK(hipMemcpyAsync(e->d_bits, bits, bb, hipMemcpyHostToDevice, e->stream));
-	rc = encode24_launch(e, e->d_bits, e->d_pcm, m, e->stream, true);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(sp, e->d_pcm, pb, hipMemcpyDeviceToHost, e->stream));
-	HIPCHK(hipMemcpyAsync(bits, e->d_bits, bb, hipMemcpyDeviceToHost, e->stream));
-	HOST_FINISH(e);
-	return 0;
+	const size_t pb = sizeof(int16_t) * MELPE_FRAME_SAMPLES * (size_t) e->channels;
+	const size_t bb = (size_t) MELPE_R24_BYTES * e->channels;
+	return engine_host_call(e, active,
+				{{sp, e->d_pcm, pb, XFER_IN | XFER_OUT}, {bits, e->d_bits, bb, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) { return encode24_kernels(e, e->d_bits, e->d_pcm, m, s); });
 }
 
 int melpe_decode2400_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
@@ -2108,22 +2154,11 @@ int melpe_decode2400_host(melpe_engine *e, int16_t *sp, const unsigned char *bit
 {
 	if (!e || !bits || !sp)
 		return fail_msg("melpe_decode2400_host: null argument");
-	DEVGUARD(e->device);
-	HOST_LOCK(e);
-	ENGINE_WAIT(e);
-	size_t pb = sizeof(int16_t) * MELPE_FRAME_SAMPLES * (size_t) e->channels;
-	size_t bb = (size_t) MELPE_R24_BYTES * e->channels;
-	int rc;
-	const uint8_t *m = stage_mask(e, active, &rc);
-	if (rc)
-		return rc;
-	HIPCHK(hipMemcpyAsync(e->d_bits, bits, bb, hipMemcpyHostToDevice, e->stream));
-	if (active)
-		HIPCHK(hipMemcpyAsync(e->d_pcm, sp, pb, hipMemcpyHostToDevice, e->stream));
-	HIPCHK((hipError_t) kl_dec24(e->d_dec, e->d_pcm, e->d_bits, m, e->channels, e->stream));
-	HIPCHK(hipMemcpyAsync(sp, e->d_pcm, pb, hipMemcpyDeviceToHost, e->stream));
-	HOST_FINISH(e);
-	return 0;
+	const size_t pb = sizeof(int16_t) * MELPE_FRAME_SAMPLES * (size_t) e->channels;
+	const size_t bb = (size_t) MELPE_R24_BYTES * e->channels;
+	return engine_host_call(e, active,
+				{{bits, e->d_bits, bb, XFER_IN}, {sp, e->d_pcm, pb, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) { return decode24_kernels(e, e->d_pcm, e->d_bits, m, s); });
 }
 
 /* per-channel state records (checkpoint / migration between engines) */
@@ -2199,13 +2234,11 @@ int melpe_synth_dev(melpe_engine *e, void *d_sp, int samples, void *hip_stream)
 {
 	if (!e || !d_sp || samples <= 0)
 		return fail_msg("melpe_synth_dev: bad arguments");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	k_synth<<<grid_for(e->channels), WAVE, 0, s>>>(
-		e->d_syn, (int16_t *) d_sp, samples, e->channels);
-	HIPCHK(hipGetLastError());
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
+		k_synth<<<grid_for(e->channels), WAVE, 0, s>>>(e->d_syn, (int16_t *) d_sp, samples, e->channels);
+		HIPCHK(hipGetLastError());
+		return 0;
+	});
 }
 
 int melpe_synth_host(uint32_t run_seed, uint32_t channel, int16_t *out, int samples)
@@ -2289,7 +2322,10 @@ void melpe_n(short *sp)
 	int16_t *d = e->d_pcm;
 	if (dg.err != hipSuccess ||
 	    hipMemcpy(d, sp, sizeof(int16_t) * n, hipMemcpyHostToDevice) != hipSuccess ||
-	    npp_launch(e, d, 1, 256, nullptr, e->stream, true, g_single_rate1200 ? 1 : 0) ||
+	    engine_call(e, e->stream, TIME_SYNC, [&](hipStream_t s) {
+		    HIPCHK((hipError_t) kl_npp(e->d_enc, d, 1, 256, nullptr, e->channels, g_single_rate1200 ? 1 : 0, s));
+		    return 0;
+	    }) ||
 	    hipMemcpy(sp, d, sizeof(int16_t) * 180, hipMemcpyDeviceToHost) != hipSuccess) {
 		fprintf(stderr, "libmelpe_amd: melpe_n failed: %s\n", g_err.c_str());
 		abort();
@@ -2306,17 +2342,23 @@ int melpe_single_reset(void)
 	return melpe_engine_reset(e, nullptr, 3);
 }
 
-void melpe_i(void)
+/* melp_ana_init + melp_syn_init, and the rate the later calls run at */
+static void single_init(const char *who, bool rate2400)
 {
 	melpe_engine *e = single_engine();
 	DevGuard dg(e->device);
 	k_melpe_i<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec);
 	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) {
-		fprintf(stderr, "libmelpe_amd: melpe_i failed\n");
+		fprintf(stderr, "libmelpe_amd: %s failed\n", who);
 		abort();
 	}
-	g_single_rate1200 = true;
-	g_single_rate2400 = false;
+	g_single_rate1200 = !rate2400;
+	g_single_rate2400 = rate2400;
+}
+
+void melpe_i(void)
+{
+	single_init("melpe_i", false);
 }
 
 /* melpe_i2 / melpe_al: the 2400 bps entry points the reference declares
@@ -2327,15 +2369,7 @@ void melpe_i(void)
  * reference's synthesis() at RATE2400). */
 void melpe_i2(void)
 {
-	melpe_engine *e = single_engine();
-	DevGuard dg(e->device);
-	k_melpe_i<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec);
-	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) {
-		fprintf(stderr, "libmelpe_amd: melpe_i2 failed\n");
-		abort();
-	}
-	g_single_rate1200 = false;
-	g_single_rate2400 = true;
+	single_init("melpe_i2", true);
 }
 
 void melpe_al(unsigned char *buf, short *sp)
@@ -2366,30 +2400,17 @@ void melpe_s(short *sp, unsigned char *buf)
 {
 	melpe_engine *e = single_engine();
 	DevGuard dg(e->device);
-	if (g_single_rate2400) {	/* synthesis() at RATE2400: 7 bytes -> 180 samples */
-		k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 0);
-		int rc = hipGetLastError() != hipSuccess || melpe_decode2400_host(e, sp, buf, nullptr);
-		if (!rc) {
-			k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 1);
-			rc = hipGetLastError() != hipSuccess ||
-			     hipStreamSynchronize(e->stream) != hipSuccess;
-		}
-		if (rc) {
-			fprintf(stderr, "libmelpe_amd: melpe_s (2400) failed: %s\n", g_err.c_str());
-			abort();
-		}
-		return;
-	}
+	/* after melpe_i2, synthesis() at RATE2400: 7 bytes -> 180 samples */
+	const bool r24 = g_single_rate2400;
 	k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 0);
-	int rc = hipGetLastError() != hipSuccess;
-	if (!rc)
-		rc = melpe_decode_host(e, sp, buf, nullptr);
+	int rc = hipGetLastError() != hipSuccess ||
+		 (r24 ? melpe_decode2400_host(e, sp, buf, nullptr) : melpe_decode_host(e, sp, buf, nullptr));
 	if (!rc) {
 		k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 1);
 		rc = hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess;
 	}
 	if (rc) {
-		fprintf(stderr, "libmelpe_amd: melpe_s failed: %s\n", g_err.c_str());
+		fprintf(stderr, "libmelpe_amd: melpe_s%s failed: %s\n", r24 ? " (2400)" : "", g_err.c_str());
 		abort();
 	}
 }
@@ -2404,9 +2425,7 @@ static int modem_state_ok(const void *d_state, int channels)
 {
 	if (!d_state || channels <= 0)
 		return fail_msg("modem: bad arguments");
-	if ((uintptr_t) d_state & 3)
-		return fail_msg("modem: state must be 4-byte aligned");
-	return 0;
+	return state_aligned("modem", d_state);
 }
 
 int melpe_modem_reset_dev(void *d_state, int channels, const void *d_mask, void *hip_stream)
@@ -2583,28 +2602,15 @@ int melpe_voice_crypt_host(unsigned char *pkts, const uint32_t *counters,
 {
 	if (!pkts || !counters || !keys || channels <= 0 || packets <= 0)
 		return fail_msg("melpe_voice_crypt_host: bad arguments");
-	size_t pb = (size_t) channels * packets * VC_PKT_BYTES;
-	size_t kb = (size_t) channels * VC_KEY_BYTES, cb = (size_t) channels * 4;
-	int dev = 0;
-	HIPCHK(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_stage[dev & 63].mu);
-	unsigned char *d = nullptr;
-	if (int r = stage_get(dev, kb + cb + channels + pb, (void **) &d))
-		return r;
-	unsigned char *dk = d, *dc = d + kb, *di = dc + cb, *dp = di + channels;
-	int rc = 0;
-	hipError_t he;
-	if ((he = hipMemcpy(dk, keys, kb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (he = hipMemcpy(dc, counters, cb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (invert && (he = hipMemcpy(di, invert, channels, hipMemcpyHostToDevice)) != hipSuccess) ||
-	    (he = hipMemcpy(dp, pkts, pb, hipMemcpyHostToDevice)) != hipSuccess)
-		rc = fail("melpe_voice_crypt_host: upload", he);
-	if (!rc)
-		rc = melpe_voice_crypt_dev(dp, dc, dk, invert ? di : nullptr, channels, packets,
-					   dir, nullptr);
-	if (!rc && (he = hipMemcpy(pkts, dp, pb, hipMemcpyDeviceToHost)) != hipSuccess)
-		rc = fail("melpe_voice_crypt_host: download", he);
-	return rc;
+	const size_t n = (size_t) channels;
+	/* the keys first: 16-byte aligned at the head of the stage buffer */
+	Xfer x[] = {{keys, nullptr, n * VC_KEY_BYTES, XFER_IN},
+		    {counters, nullptr, n * 4, XFER_IN},
+		    {invert, nullptr, n, XFER_IN},
+		    {pkts, nullptr, n * packets * VC_PKT_BYTES, XFER_IN | XFER_OUT}};
+	return stage_host_call("melpe_voice_crypt_host", x, 4, [&] {
+		return melpe_voice_crypt_dev(x[3].dev, x[1].dev, x[0].dev, x[2].dev, channels, packets, dir, nullptr);
+	});
 }
 
 
@@ -2629,8 +2635,8 @@ static int link_args(const char *who, const void *state, const void *pkts, const
 		return fail_msg(w + ": null packet pointer");
 	if (!ret)
 		return fail_msg(w + ": null return-value pointer");
-	if ((uintptr_t) state & 3)
-		return fail_msg(w + ": state must be 4-byte aligned");
+	if (int rc = state_aligned(who, state))
+		return rc;
 	if (dev && (((uintptr_t) pkts & 3) || ((uintptr_t) ret & 3)))
 		return fail_msg(w + ": packets and return values must be 4-byte aligned");
 	if ((long) channels * packets > 0x7fffffffL / VC_PKT_BYTES)
@@ -2669,35 +2675,17 @@ static int link_host(bool tx, void *state, unsigned char *pkts, uint8_t *flag, i
 	if (int rc = link_args(who, state, pkts, ret, channels, packets, false))
 		return rc;
 	const size_t n = (size_t) channels * packets;
-	const size_t sb = (size_t) channels * LINK_STATE_BYTES, rb = n * 4, pb = (n * VC_PKT_BYTES + 3) & ~(size_t) 3;
-	const size_t fb = (n + 3) & ~(size_t) 3;
-	int dev = 0;
-	HIPCHK(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_stage[dev & 63].mu);
-	unsigned char *d = nullptr;
-	if (int r = stage_get(dev, sb + rb + pb + fb + channels, (void **) &d))
-		return r;
-	unsigned char *ds = d, *dr = ds + sb, *dp = dr + rb, *df = dp + pb, *da = df + fb;
-	hipError_t he;
 	/* an inactive or refused channel keeps its outputs: ret (and RX voice) go up too */
-	if ((he = hipMemcpy(ds, state, sb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (he = hipMemcpy(dr, ret, rb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (he = hipMemcpy(dp, pkts, n * VC_PKT_BYTES, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (flag && (he = hipMemcpy(df, flag, n, hipMemcpyHostToDevice)) != hipSuccess) ||
-	    (active && (he = hipMemcpy(da, active, channels, hipMemcpyHostToDevice)) != hipSuccess))
-		return fail((std::string(who) + ": upload").c_str(), he);
-	int rc = tx ? melpe_link_tx_dev(ds, dp, flag ? df : nullptr, dr, channels, packets, active ? da : nullptr,
-					nullptr)
-		    : melpe_link_rx_dev(ds, dp, dr, flag ? df : nullptr, channels, packets,
-					active ? da : nullptr, nullptr);
-	if (rc)
-		return rc;
-	if ((he = hipMemcpy(state, ds, sb, hipMemcpyDeviceToHost)) != hipSuccess ||
-	    (he = hipMemcpy(ret, dr, rb, hipMemcpyDeviceToHost)) != hipSuccess ||
-	    (he = hipMemcpy(pkts, dp, n * VC_PKT_BYTES, hipMemcpyDeviceToHost)) != hipSuccess ||
-	    (!tx && flag && (he = hipMemcpy(flag, df, n, hipMemcpyDeviceToHost)) != hipSuccess))
-		return fail((std::string(who) + ": download").c_str(), he);
-	return 0;
+	Xfer x[] = {{state, nullptr, (size_t) channels * LINK_STATE_BYTES, XFER_IN | XFER_OUT},
+		    {ret, nullptr, n * 4, XFER_IN | XFER_OUT},
+		    {pkts, nullptr, n * VC_PKT_BYTES, XFER_IN | XFER_OUT},
+		    {flag, nullptr, n, tx ? XFER_IN : XFER_IN | XFER_OUT},
+		    {active, nullptr, (size_t) channels, XFER_IN}};
+	return stage_host_call(who, x, 5, [&] {
+		return tx ? melpe_link_tx_dev(x[0].dev, x[2].dev, x[3].dev, x[1].dev, channels, packets, x[4].dev, nullptr)
+			  : melpe_link_rx_dev(x[0].dev, x[2].dev, x[1].dev, x[3].dev, channels, packets, x[4].dev,
+					      nullptr);
+	});
 }
 
 int melpe_link_tx_host(void *state, unsigned char *pkts, const uint8_t *voiced, int32_t *ret, int channels,
@@ -2732,8 +2720,8 @@ int melpe_vad_reset_dev(void *d_state, int channels, const void *d_mask, void *h
 {
 	if (!d_state || channels <= 0)
 		return fail_msg("melpe_vad_reset_dev: bad arguments");
-	if ((uintptr_t) d_state & 3)
-		return fail_msg("melpe_vad_reset_dev: state must be 4-byte aligned");
+	if (int rc = state_aligned("melpe_vad_reset_dev", d_state))
+		return rc;
 	k_vad_reset<<<grid_for(channels), WAVE, 0, (hipStream_t) hip_stream>>>(
 		(VadState *) d_state, (const uint8_t *) d_mask, channels);
 	HIPCHK(hipGetLastError());
@@ -2745,13 +2733,9 @@ int melpe_vad_dev(void *d_state, const void *d_sp, void *d_votes, int channels,
 {
 	if (!d_state || !d_sp || !d_votes || channels <= 0)
 		return fail_msg("melpe_vad_dev: bad arguments");
-	if ((uintptr_t) d_state & 3)
-		return fail_msg("melpe_vad_dev: state must be 4-byte aligned");
-	k_vad<<<grid_for(channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(VadState *) d_state, (const int16_t *) d_sp, (uint8_t *) d_votes, nullptr,
-		(const uint8_t *) d_active, channels);
-	HIPCHK(hipGetLastError());
-	return 0;
+	if (int rc = state_aligned("melpe_vad_dev", d_state))
+		return rc;
+	return vad_launch(d_state, d_sp, d_votes, nullptr, d_active, channels, (hipStream_t) hip_stream);
 }
 
 int melpe_vad_host(unsigned char *state, const int16_t *sp, uint8_t *votes, int channels,
@@ -2759,28 +2743,15 @@ int melpe_vad_host(unsigned char *state, const int16_t *sp, uint8_t *votes, int 
 {
 	if (!state || !sp || !votes || channels <= 0)
 		return fail_msg("melpe_vad_host: bad arguments");
-	size_t sb = sizeof(VadState) * (size_t) channels;
-	size_t pb = sizeof(int16_t) * MELPE_SF_SAMPLES * (size_t) channels;
-	int dev = 0;
-	HIPCHK(hipGetDevice(&dev));
-	std::lock_guard<std::mutex> lk(g_stage[dev & 63].mu);
-	unsigned char *d = nullptr;
-	if (int r = stage_get(dev, sb + pb + 2 * (size_t) channels, (void **) &d))
-		return r;
-	unsigned char *ds = d, *dp = d + sb, *dv = dp + pb, *da = dv + channels;
-	int rc = 0;
-	hipError_t he;
-	if ((he = hipMemcpy(ds, state, sb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (he = hipMemcpy(dp, sp, pb, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (he = hipMemcpy(dv, votes, channels, hipMemcpyHostToDevice)) != hipSuccess ||
-	    (active && (he = hipMemcpy(da, active, channels, hipMemcpyHostToDevice)) != hipSuccess))
-		rc = fail("melpe_vad_host: upload", he);
-	if (!rc)
-		rc = melpe_vad_dev(ds, dp, dv, channels, active ? da : nullptr, nullptr);
-	if (!rc && ((he = hipMemcpy(state, ds, sb, hipMemcpyDeviceToHost)) != hipSuccess ||
-		    (he = hipMemcpy(votes, dv, channels, hipMemcpyDeviceToHost)) != hipSuccess))
-		rc = fail("melpe_vad_host: download", he);
-	return rc;
+	const size_t n = (size_t) channels;
+	/* an inactive channel keeps its votes: they go up too */
+	Xfer x[] = {{state, nullptr, sizeof(VadState) * n, XFER_IN | XFER_OUT},
+		    {sp, nullptr, sizeof(int16_t) * MELPE_SF_SAMPLES * n, XFER_IN},
+		    {votes, nullptr, n, XFER_IN | XFER_OUT},
+		    {active, nullptr, n, XFER_IN}};
+	return stage_host_call("melpe_vad_host", x, 4, [&] {
+		return melpe_vad_dev(x[0].dev, x[1].dev, x[2].dev, channels, x[3].dev, nullptr);
+	});
 }
 
 
@@ -2789,13 +2760,11 @@ int melpe_tx_dev(melpe_engine *e, void *d_vad_state, void *d_bits, void *d_sp, v
 {
 	if (!e || !d_vad_state || !d_bits || !d_sp || !d_votes || !d_gate)
 		return fail_msg("melpe_tx_dev: bad arguments");
-	if ((uintptr_t) d_vad_state & 3)
-		return fail_msg("melpe_tx_dev: state must be 4-byte aligned");
+	if (int rc = state_aligned("melpe_tx_dev", d_vad_state))
+		return rc;
 	DEVGUARD(e->device);
-	k_vad<<<grid_for(e->channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(VadState *) d_vad_state, (const int16_t *) d_sp, (uint8_t *) d_votes,
-		(uint8_t *) d_gate, (const uint8_t *) d_active, e->channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = vad_launch(d_vad_state, d_sp, d_votes, d_gate, d_active, e->channels, (hipStream_t) hip_stream))
+		return rc;
 	return melpe_encode_dev(e, d_bits, d_sp, d_gate, hip_stream);
 }
 
@@ -2807,13 +2776,11 @@ int melpe_tx_npp_dev(melpe_engine *e, void *d_vad_state, void *d_sp, void *d_vot
 {
 	if (!e || !d_vad_state || !d_sp || !d_votes || !d_gate)
 		return fail_msg("melpe_tx_npp_dev: bad arguments");
-	if ((uintptr_t) d_vad_state & 3)
-		return fail_msg("melpe_tx_npp_dev: state must be 4-byte aligned");
+	if (int rc = state_aligned("melpe_tx_npp_dev", d_vad_state))
+		return rc;
 	DEVGUARD(e->device);
-	k_vad<<<grid_for(e->channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(VadState *) d_vad_state, (const int16_t *) d_sp, (uint8_t *) d_votes,
-		(uint8_t *) d_gate, (const uint8_t *) d_active, e->channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = vad_launch(d_vad_state, d_sp, d_votes, d_gate, d_active, e->channels, (hipStream_t) hip_stream))
+		return rc;
 	return melpe_encode_npp_dev(e, d_sp, d_gate, hip_stream);
 }
 
@@ -2831,33 +2798,12 @@ int melpe_tx_pipe_dev(melpe_engine *e, void *d_vad_state, void *d_bits, const vo
 	if (!e || !d_vad_state || !d_bits || !d_sp || !d_gate ||
 	    (d_sp_next && (!d_votes_next || !d_gate_next)))
 		return fail_msg("melpe_tx_pipe_dev: bad arguments");
-	if ((uintptr_t) d_vad_state & 3)
-		return fail_msg("melpe_tx_pipe_dev: state must be 4-byte aligned");
+	if (int rc = state_aligned("melpe_tx_pipe_dev", d_vad_state))
+		return rc;
 	if (d_sp_next == d_sp || (d_sp_next && d_gate_next == d_gate))
 		return fail_msg("melpe_tx_pipe_dev: the next superframe's buffers must be other buffers");
-	DEVGUARD(e->device);
-	if (d_sp_next)
-		if (int rc = side_streams(e))
-			return rc;
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
-	HIPCHK((hipError_t) ana_launch(e, (const int16_t *) d_sp, (uint8_t *) d_bits, (const uint8_t *) d_gate, s,
-				       d_sp_next ? e->ev_pin : nullptr));
-	ev_end(e, s, false);
-	if (d_sp_next) {
-		const hipStream_t ns = e->cin;
-		HIPCHK(hipStreamWaitEvent(ns, e->ev_pin, 0));
-		k_vad<<<grid_for(e->channels), WAVE, 0, ns>>>((VadState *) d_vad_state, (const int16_t *) d_sp_next,
-							      (uint8_t *) d_votes_next, (uint8_t *) d_gate_next,
-							      (const uint8_t *) d_active_next, e->channels);
-		HIPCHK(hipGetLastError());
-		HIPCHK((hipError_t) kl_enc_npp(e->d_enc, (int16_t *) d_sp_next, (const uint8_t *) d_gate_next,
-					       e->channels, ns));
-		HIPCHK(hipEventRecord(e->ev_npp, ns));
-		HIPCHK(hipStreamWaitEvent(s, e->ev_npp, 0));
-	}
-	return _call.finish();
+	const PipeNext nx = {d_sp_next, d_gate_next, d_vad_state, d_votes_next, d_active_next};
+	return pipe_step(e, d_bits, d_sp, d_gate, d_sp_next ? &nx : nullptr, nullptr, (hipStream_t) hip_stream);
 }
 
 
@@ -2942,23 +2888,20 @@ int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos
 	    ((uintptr_t) d_sp & 7))
 		return fail_msg("melpe_rx_stream_dev: pos, end and pos_next must be 4-byte and "
 				"sp 8-byte aligned");
-	DEVGUARD(e->device);
-	hipStream_t s = (hipStream_t) hip_stream;
-	ENGINE_CALL(e, s);
-	ev_begin(e, s);
 	const int n = e->channels;
-	k_stream_parse<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
-		(const unsigned char *) d_stream, (const uint32_t *) d_pos, (const uint32_t *) d_end,
-		(uint32_t *) d_pos_next, (unsigned char *) d_bits, (uint8_t *) d_voiced,
-		(uint8_t *) d_lens, (const uint8_t *) d_active, n);
-	HIPCHK(hipGetLastError());
-	k_stream_zero<<<(unsigned) (((long) n + STREAM_BLOCK / WAVE - 1) / (STREAM_BLOCK / WAVE)),
-			STREAM_BLOCK, 0, s>>>((uint2 *) d_sp, (const uint8_t *) d_lens, n);
-	HIPCHK(hipGetLastError());
-	HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
-				       (const uint8_t *) d_voiced, s));
-	ev_end(e, s, false);
-	return _call.finish();
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		k_stream_parse<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
+			(const unsigned char *) d_stream, (const uint32_t *) d_pos, (const uint32_t *) d_end,
+			(uint32_t *) d_pos_next, (unsigned char *) d_bits, (uint8_t *) d_voiced,
+			(uint8_t *) d_lens, (const uint8_t *) d_active, n);
+		HIPCHK(hipGetLastError());
+		k_stream_zero<<<(unsigned) (((long) n + STREAM_BLOCK / WAVE - 1) / (STREAM_BLOCK / WAVE)),
+				STREAM_BLOCK, 0, s>>>((uint2 *) d_sp, (const uint8_t *) d_lens, n);
+		HIPCHK(hipGetLastError());
+		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
+					       (const uint8_t *) d_voiced, s));
+		return 0;
+	});
 }
 
 }  // extern "C"

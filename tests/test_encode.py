@@ -215,6 +215,76 @@ def test_encode_host_two_threads_one_engine():
 
 
 @pytest.mark.gpu
+def test_encode_pipe_two_threads_first_calls_one_engine():
+    """Two host threads whose first pipelined calls on one fresh engine come
+    together (melpe_batch.h: one engine may be called from several host
+    threads): 128 channels, so the halves c % 2 share both waves; each thread
+    on its own torch stream and device buffers runs melpe_encode_npp_dev and
+    then six pipelined superframes under its half as the mask, one of them
+    through melpe_duplex_pipe_dev with a decode of zero bits, so the engine
+    makes cout / cin and cdec while the other thread calls.  Each half's bits
+    and in-place NPP output equal one engine running all channels serially.
+    This pins the supported behaviour; it runs once and cannot be made to
+    fail reliably on an engine that creates its side streams outside the
+    lock -- that they are made under it and published whole is shown by
+    reading engine.hip engine_streams."""
+    import threading
+    import torch
+    from pairphone_amd import MelpeEngine
+    g = golden()
+    C, nsf = 128, 6
+    x = signals(g["seed"], C, nsf)
+    dev = torch.device("cuda", 0)
+    halves = [np.arange(C) % 2 == h for h in (0, 1)]
+    xs = np.ascontiguousarray(x.reshape(C, nsf, 540).transpose(1, 0, 2))
+    buf = []
+    for h in (0, 1):
+        buf.append({"s": torch.cuda.Stream(dev), "x": torch.from_numpy(xs).to(dev),
+                    "bits": torch.zeros((nsf, C, 11), dtype=torch.uint8, device=dev),
+                    "mask": torch.from_numpy(halves[h].astype(np.uint8)).to(dev),
+                    "zero": torch.zeros((C, 11), dtype=torch.uint8, device=dev),
+                    "pcm": torch.zeros((C, 540), dtype=torch.int16, device=dev)})
+    torch.cuda.synchronize(dev)
+    eng = MelpeEngine(C)
+    start = threading.Barrier(2)
+    err = []
+
+    def worker(h):
+        try:
+            b = buf[h]
+            s, m, xd = b["s"].cuda_stream, b["mask"].data_ptr(), b["x"]
+            start.wait()
+            eng.encode_npp_dev(xd[0].data_ptr(), m, s)
+            for k in range(nsf):
+                nxt = xd[k + 1].data_ptr() if k + 1 < nsf else None
+                if h:
+                    eng.duplex_pipe_dev(b["bits"][k].data_ptr(), xd[k].data_ptr(), nxt, b["pcm"].data_ptr(),
+                                        b["zero"].data_ptr(), d_active=m, d_active_next=m, d_dec_active=m,
+                                        stream=s)
+                else:
+                    eng.encode_pipe_dev(b["bits"][k].data_ptr(), xd[k].data_ptr(), nxt, d_active=m,
+                                        d_active_next=m, stream=s)
+        except Exception as e:  # noqa: BLE001
+            err.append(e)
+    th = [threading.Thread(target=worker, args=(h,)) for h in (0, 1)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join()
+    torch.cuda.synchronize(dev)
+    eng.close()
+    assert not err, err
+    ref = MelpeEngine(C)
+    want, wnpp = run_superframes(ref.encode, x.copy(), nsf)
+    ref.close()
+    for h in (0, 1):
+        bits = buf[h]["bits"].cpu().numpy().transpose(1, 0, 2).reshape(C, nsf * 11)
+        npp = buf[h]["x"].cpu().numpy().transpose(1, 0, 2).reshape(C, nsf * 540)
+        np.testing.assert_array_equal(bits[halves[h]], want[halves[h]])
+        np.testing.assert_array_equal(npp[halves[h]], wnpp[halves[h]])
+
+
+@pytest.mark.gpu
 def test_encode_host_async_matches_sync():
     """The host-fed pipeline (melpe_encode_host_async: two device slots,
     copies and kernels on three streams) against melpe_encode_host, on
