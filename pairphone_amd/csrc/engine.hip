@@ -11,6 +11,8 @@
  *   k_npp.hip  melpe_n, and the NPP half of melpe_a (melpe/melpe.c:94-96)
  *   k_ana.hip  the analysis half of melpe_a (melpe/melpe.c:97-98)
  *   k_dec.hip  melpe_s (melpe/melpe.c:102-107)
+ * and the rest that kern.h lists; launch.h declares what this file calls in
+ * them.
  * Execution model: one lane per channel (kern.h).  Per-channel
  * state lives in HBM (EncState / DecState), the codebooks in each TU's
  * constant tables (uploaded once per device).
@@ -56,78 +58,6 @@ extern "C" const unsigned char melpe_tables_blob[];
 extern "C" const unsigned char melpe_tables_blob_end[];
 
 MELPE_TU(eng)
-
-/* kernels of the other translation units (k_npp.hip, k_ana.hip, k_dec.hip) */
-extern "C" {
-int melpe_tu_npp_upload(const void *blob, size_t bytes);
-int melpe_tu_ana_upload(const void *blob, size_t bytes);
-int melpe_tu_anamw_upload(const void *blob, size_t bytes);
-int melpe_tu_harm_upload(const void *blob, size_t bytes);
-int melpe_tu_dec_upload(const void *blob, size_t bytes);
-int melpe_tu_r24_upload(const void *blob, size_t bytes);
-int melpe_tu_dspeval_upload(const void *blob, size_t bytes);
-int melpe_tu_par_upload(const void *blob, size_t bytes);
-int melpe_tu_r24_prof(uint64_t *acc);
-int melpe_tu_npp_prof(uint64_t *acc);
-int melpe_tu_ana_prof(uint64_t *acc);
-int melpe_tu_anamw_prof(uint64_t *acc);
-int melpe_tu_harm_prof(uint64_t *acc);
-int melpe_tu_dec_prof(uint64_t *acc);
-int kl_npp(EncState *enc, int16_t *sp, int frames, int stride, const uint8_t *active, int n,
-	   int rate1200, hipStream_t s);
-int kl_enc_npp(EncState *enc, int16_t *sp, const uint8_t *active, int n, hipStream_t s);
-int kl_enc_ana(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active, int n,
-	       const int *perm, const int *nlive, int16_t *res, AnaGate gate, hipStream_t s);
-int kl_enc_harm(EncState *enc, const int16_t *res, const uint8_t *active, int n, const int *perm,
-		const int *nlive, AnaGate gate, hipStream_t s);
-int kl_enc_tail(EncState *enc, uint8_t *bits, const uint8_t *active, int n, const int *perm,
-		const int *nlive, AnaGate gate, hipStream_t s);
-int kl_enc_ana_mw(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active, int n,
-		  const int *perm, const int *nlive, int nw, uint32_t *lqbuf, AnaGate gate, hipStream_t s);
-size_t kl_enc_ana_mw_lq_words(int n);
-int kl_enc_ana_dbg(EncState *enc, const int16_t *sp, int n, int upto, hipStream_t s);
-/* the function-level parity test (dsp_eval.h): lane and blob-table scalar
- * modes in k_dsp_eval.hip, the wave forms next to the code they test */
-int kl_dsp_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
-int kl_dsp_scalar(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
-int kl_dsp_scalar_lds(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
-int kl_dsp_wave_fft(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
-int kl_dsp_wave_harm(const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
-int kl_npp_warm(int n, hipStream_t s);
-int kl_ana_warm(int n, hipStream_t s);
-int kl_harm_warm(int n, hipStream_t s);
-int kl_ana_mw_warm(int n, hipStream_t s);
-int kl_dec_warm(int n, hipStream_t s);
-int kl_dec2_warm(int n, hipStream_t s);
-size_t kl_ana_private(void);
-size_t kl_ana_mw_private(void);
-size_t kl_harm_private(void);
-size_t kl_harm_wave_private(void);
-size_t kl_npp_private(void);
-size_t kl_dec_private(void);
-size_t kl_dec2_private(void);
-size_t kl_decode2_hb_words(int n);
-int kl_decode2(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
-	       const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s);
-int kl_decode(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
-	      const int *perm, const int *nlive,
-	      hipStream_t s);
-int kl_enc24(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active, int n,
-	     hipStream_t s);
-int kl_dec24(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
-	     hipStream_t s);
-/* the parameter tap and the parse-only decoder (k_par.hip) */
-int kl_par_tap(const void *rec, size_t stride, size_t off, void *par, void *qpar, const uint8_t *active,
-	       int n, hipStream_t s);
-int kl_parse(DecState *dec, void *par, const uint8_t *bits, const uint8_t *active, int n, hipStream_t s);
-size_t kl_parse_private(void);
-/* the link's packet layer and the Golay sweep (k_link.hip) */
-int kl_link_tx(void *st, void *pkts, const void *voiced, void *ret, const void *active, int channels,
-	       int packets, hipStream_t s);
-int kl_link_rx(void *st, void *pkts, void *ret, void *voice, const void *active, int channels, int packets,
-	       hipStream_t s);
-int kl_golay_sweep(void *enc, void *digest, hipStream_t s);
-}
 
 /* ------------------------------------------------------------------ */
 /* small kernels: reset, init, parameter sharing, test-signal synth   */
@@ -687,16 +617,18 @@ static int stage_get(int dev, size_t bytes, void **out)
  * O(L^2) in realIDFT and a frame holds 180/L of them, the analysis windows
  * and harmonic counts follow the pitch, and unvoiced frames take other
  * branches.  A wave pays the slowest of its 64 channels in every such loop.
- * So before each launch the live channels are counting-sorted into 128
+ * So before each launch the live channels are counting-sorted into 568
  * classes -- voiced frames of the channel's last superframe (0..3) x its last
- * pitch in 3-sample steps -- and lane g of the kernel runs channel perm[g];
+ * pitch in 1-sample steps -- and lane g of the kernel runs channel perm[g];
  * lanes at or past the live count exit at once, so a ragged mask also packs
  * the live channels into the fewest waves.  Each channel's arithmetic is
  * untouched (the order only decides which channels share a wave), so the
  * output is the same bit for bit; the order within a class follows the
  * atomics and is not reproducible, which nothing depends on.
  */
-#define NBIN 640	/* the largest class count of any key (MELPE_BIN_KEY 3: 4 x 141) */
+#define BIN_PITCHES 142	/* pitch classes: 20 .. 161 samples in 1-sample steps */
+#define NBIN 640	/* room for the 4 x BIN_PITCHES = 568 classes (progprio.h and AnaGate index past it) */
+static_assert(4 * BIN_PITCHES <= NBIN, "every class has a counter");
 #define NOT_LIVE 0xffff	/* the key of a channel that is not live */
 static_assert(NBIN < NOT_LIVE, "class ids and the not-live mark must fit the uint16 keys");
 struct BinBuf {
@@ -735,44 +667,22 @@ static hipError_t bin_alloc(BinBuf *b, int channels)
 }
 
 /* the class of one record, from its last superframe: the voiced frames
- * (quant_par uv_flag, 0 = voiced) and the pitch (Q7) of its frames.
- * MELPE_BIN_KEY: 3 (default) = voiced count x last pitch in 1-sample steps
- * (568 classes), 4 = the same in 2-sample steps, 0 = in 3-sample steps (the
- * round-2 key), 1 = mean pitch in 2-sample steps, 2 = voiced count x last
- * pitch in 5-sample steps.  Round 5, MI355X, 262,144 channels, two runs
- * each (profiles/r05_s_keys.txt): k_decode 8.52 -> 8.39 ms and the analysis
- * 31.11 -> 31.01 ms from key 0 to key 3. */
-__device__ __forceinline__ int bin_class(const char *rec, int off_par, int off_uv, int mode)
+ * (quant_par uv_flag, 0 = voiced) and the pitch (Q7) of its last frame, in
+ * 1-sample steps.  Coarser steps (2, 3, 5 samples) and the mean pitch lost
+ * to this key in round 5 on MI355X at 262,144 channels, two runs each
+ * (profiles/r05_s_keys.txt): k_decode 8.52 -> 8.39 ms and the analysis
+ * 31.11 -> 31.01 ms from the 3-sample key to this one. */
+__device__ __forceinline__ int bin_class(const char *rec, int off_par, int off_uv)
 {
 	const int16_t *uv = (const int16_t *) (rec + off_uv);
-	int nv = (uv[0] == 0) + (uv[1] == 0) + (uv[2] == 0);
-	int p[NF];
-	for (int k = 0; k < NF; k++)
-		p[k] = *(const int16_t *) (rec + off_par + k * sizeof(MelpParam)) >> 7;
-	int b;
-	if (mode == 1) {
-		b = ((p[0] + p[1] + p[2]) / 3 - 20) / 2;
-		return b < 0 ? 0 : (b > 127 ? 127 : b);
-	}
-	if (mode == 3 || mode == 4) {	/* voiced count x last pitch in 1- / 2-sample steps */
-		const int step = mode == 3 ? 1 : 2, nc = 141 / step + 1;
-		b = (p[NF - 1] - 20) / step;
-		b = b < 0 ? 0 : (b > nc - 1 ? nc - 1 : b);
-		return nv * nc + b;
-	}
-	if (mode == 2) {
-		b = (p[NF - 1] - 20) / 5;
-		b = b < 0 ? 0 : (b > 15 ? 15 : b);
-		return nv * 16 + b;
-	}
-	b = (p[NF - 1] - 20) / 3;
-	b = b < 0 ? 0 : (b > 31 ? 31 : b);
-	return nv * 32 + b;
+	const int nv = (uv[0] == 0) + (uv[1] == 0) + (uv[2] == 0);
+	int b = (*(const int16_t *) (rec + off_par + (NF - 1) * sizeof(MelpParam)) >> 7) - 20;
+	b = b < 0 ? 0 : (b > BIN_PITCHES - 1 ? BIN_PITCHES - 1 : b);
+	return nv * BIN_PITCHES + b;
 }
 
 __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t stride, int off_par,
-						   int off_uv, const uint8_t *active, int n, BinBuf b,
-						   int mode)
+						   int off_uv, const uint8_t *active, int n, BinBuf b)
 {
 	__shared__ unsigned cnt[NBIN];
 	for (int k = threadIdx.x; k < NBIN; k += blockDim.x)
@@ -782,7 +692,7 @@ __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t strid
 	if (c < n) {
 		int k = NOT_LIVE;
 		if (!active || active[c]) {
-			k = bin_class(rec + (size_t) c * stride, off_par, off_uv, mode);
+			k = bin_class(rec + (size_t) c * stride, off_par, off_uv);
 			atomicAdd(&cnt[k], 1u);
 		}
 		b.key[c] = (uint16_t) k;
@@ -829,27 +739,12 @@ __global__ __launch_bounds__(256) void k_bin_scatter(int n, BinBuf b)
 
 static bool bin_enabled(void)
 {
-	static int v = -1;
-	if (v < 0) {
-		const char *s = getenv("MELPE_BIN");
-		v = !(s && s[0] == '0');
-	}
-	return v != 0;
+	static const bool on = env_int("MELPE_BIN", 1) != 0;
+	return on;
 }
 
 /* sorts the live channels of `rec` (records of `stride` bytes) into b.perm on
- * stream s; false when the order is off (identity lanes + mask) */
-static int bin_key_mode(void)
-{
-	static int v = -1;
-	if (v < 0) {
-		const char *s = getenv("MELPE_BIN_KEY");
-		v = s ? atoi(s) : 3;
-	}
-	return v;
-}
-
-/* *on: whether the order is used (false: identity lanes + mask) */
+ * stream s; *on: whether the order is used (false: identity lanes + mask) */
 static hipError_t bin_launch(int order, BinBuf &b, const void *rec, size_t stride, int off_par,
 			     int off_uv, const uint8_t *active, int n, hipStream_t s, bool *on)
 {
@@ -862,8 +757,7 @@ static hipError_t bin_launch(int order, BinBuf &b, const void *rec, size_t strid
 	unsigned g = (unsigned) ((n + 255) / 256);
 	if ((er = hipMemsetAsync(b.ctl, 0, sizeof(unsigned) * NBIN, s)) != hipSuccess)
 		return er;
-	k_bin_count<<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b,
-				      bin_key_mode());
+	k_bin_count<<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
 	if ((er = hipGetLastError()) != hipSuccess)
 		return er;
 	k_bin_scan<<<1, WAVE, 0, s>>>(b);
@@ -946,42 +840,17 @@ struct melpe_engine {
  * about four waves per SIMD to hide its scratch latency; below that the
  * channel count leaves SIMDs idle or alone, and the multi-wave kernel
  * (k_enc_ana_mw, ana_mw.h) spreads each channel's independent chains over
- * 2 or 4 waves instead.  MELPE_ANA_NW overrides the automatic choice
- * (diagnostics), not an explicit melpe_engine_set_ana_waves(1 or 4).
+ * 4 waves instead.  melpe_engine_set_ana_waves(1 or 4) overrides the
+ * automatic choice.
  */
-static int ana_nw_env(void)
-{
-	static int env = -2;
-	if (env == -2) {
-		const char *v = getenv("MELPE_ANA_NW");
-		env = v ? atoi(v) : -1;
-	}
-	return env;
-}
-
 static int ana_waves_for(melpe_engine *e)
 {
-	const int env = ana_nw_env();
-	/* an explicit melpe_engine_set_ana_waves() wins over the environment */
-	int nw = e->ana_waves ? e->ana_waves : env;
-	if (nw == 1 || nw == 4)
-		return nw;
+	if (e->ana_waves == 1 || e->ana_waves == 4)
+		return e->ana_waves;
 	/* k_enc_ana_mw holds two workgroups (of 4 waves) per CU, so it keeps
 	 * every workgroup resident up to 512 of them: 32,768 channels */
 	long groups = (e->channels + WAVE - 1) / WAVE;
 	return groups <= 512 ? 4 : 1;
-}
-
-/* the split lane analysis (k_harm.hip); MELPE_HARM=0 (diagnostics) runs the
- * whole analysis in k_enc_ana */
-static bool harm_split(void)
-{
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MELPE_HARM");
-		v = !(e && e[0] == '0');
-	}
-	return v != 0;
 }
 
 /* after_sort: recorded on s between the lane-order sort and the analysis
@@ -1014,8 +883,7 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 	 * No host readback, so host run-ahead cannot make the choice stale.
 	 * Either mapping gives the same bits (the four-wave kernel grid-strides
 	 * over every live slot). */
-	const bool dual = nw == 1 && on && e->ana_waves == 0 && ana_nw_env() < 0 &&
-			  e->mw_live_max > 0 && harm_split();
+	const bool dual = nw == 1 && on && e->ana_waves == 0 && e->mw_live_max > 0;
 	AnaGate lane = all, mw = all;
 	if (dual) {
 		lane.lo = e->mw_live_max;
@@ -1023,20 +891,16 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 	}
 	int rc = 0;
 	if (dual || nw == 4)
-		rc = kl_enc_ana_mw(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, 4, e->d_lq, mw, s);
+		rc = kl_enc_ana_mw(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_lq, mw, s);
 	if (rc == 0 && nw == 1) {
-		if (harm_split()) {
-			/* lane-per-channel analysis up to the Fourier magnitudes,
-			 * the magnitudes with a wave per channel, then the packing
-			 * (k_harm.hip) */
-			rc = kl_enc_ana(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_res, lane, s);
-			if (rc == 0)
-				rc = kl_enc_harm(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
-			if (rc == 0)
-				rc = kl_enc_tail(e->d_enc, d_bits, d_act, e->channels, perm, nlive, lane, s);
-		} else {
-			rc = kl_enc_ana(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, nullptr, lane, s);
-		}
+		/* lane-per-channel analysis up to the Fourier magnitudes, the
+		 * magnitudes with a wave per channel, then the packing
+		 * (k_harm.hip) */
+		rc = kl_enc_ana(e->d_enc, d_sp, d_act, e->channels, perm, nlive, e->d_res, lane, s);
+		if (rc == 0)
+			rc = kl_enc_harm(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
+		if (rc == 0)
+			rc = kl_enc_tail(e->d_enc, d_bits, d_act, e->channels, perm, nlive, lane, s);
 	}
 	if (rc == 0 && on)
 		rc = (int) bin_release(b, s);
@@ -1045,16 +909,11 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 
 /* Waves per 64 channels of the decoder: 1 = one lane per channel
  * (k_decode); 2 = the two-wave decoder (k_decode2), for channel counts that
- * leave SIMDs idle in lane mode.  MELPE_DEC_NW overrides the automatic
- * choice (diagnostics), not an explicit melpe_engine_set_dec_waves. */
+ * leave SIMDs idle in lane mode.  melpe_engine_set_dec_waves(1 or 2)
+ * overrides the automatic choice. */
 static int dec_waves_for(melpe_engine *e)
 {
-	static int env = -2;
-	if (env == -2) {
-		const char *v = getenv("MELPE_DEC_NW");
-		env = v ? atoi(v) : -1;
-	}
-	int nw = e->dec_waves ? e->dec_waves : env;
+	int nw = e->dec_waves;
 	if (nw != 1 && nw != 2)
 		nw = e->channels <= DEC2_MAX_CHANNELS ? 2 : 1;
 	return nw == 2 && e->d_hb ? 2 : 1;
@@ -1104,10 +963,9 @@ static int ensure_device_tables(int dev)
 	if (bytes != sizeof(int16_t) * MELPE_TABLE_WORDS)
 		return fail_msg("embedded table blob has the wrong size");
 	DEVGUARD(dev);
-	int (*up[])(const void *, size_t) = {melpe_tu_eng_upload, melpe_tu_npp_upload,
-					     melpe_tu_ana_upload, melpe_tu_anamw_upload, melpe_tu_harm_upload,
-					     melpe_tu_dec_upload, melpe_tu_r24_upload,
-					     melpe_tu_dspeval_upload, melpe_tu_par_upload};
+#define TU_UPLOAD(name) melpe_tu_##name##_upload,
+	int (*up[])(const void *, size_t) = {MELPE_TU_LIST(TU_UPLOAD)};
+#undef TU_UPLOAD
 	for (auto f : up)
 		if (int rc = f(melpe_tables_blob, bytes))
 			return fail("table upload", (hipError_t) rc);
@@ -1503,8 +1361,7 @@ static int engine_reserve(melpe_engine *e)
 {
 	DEVGUARD(e->device);
 	hipError_t er;
-	if (harm_split() && (er = hipMalloc(&e->d_res, sizeof(int16_t) * NF * LPC_FRAME *
-						     (size_t) e->channels)) != hipSuccess) {
+	if ((er = hipMalloc(&e->d_res, sizeof(int16_t) * NF * LPC_FRAME * (size_t) e->channels)) != hipSuccess) {
 		e->d_res = nullptr;
 		return fail("melpe_engine_create: analysis residual buffer", er);
 	}
@@ -2018,14 +1875,16 @@ static int params_kernels(melpe_engine *e, int which, void *d_par, void *d_qpar,
 			  const void *d_active, hipStream_t s)
 {
 	const uint8_t *d_act = (const uint8_t *) d_active;
+	uint32_t *par = (uint32_t *) d_par;
 	if (which == 0)
-		HIPCHK((hipError_t) kl_par_tap(e->d_enc, sizeof(EncState), offsetof(EncState, a) + offsetof(EncAna, par),
-					       d_par, d_qpar, d_act, e->channels, s));
-	else if (which == 1)
-		HIPCHK((hipError_t) kl_par_tap(e->d_dec, sizeof(DecState), offsetof(DecState, par), d_par, nullptr,
+		HIPCHK((hipError_t) kl_par_tap((const char *) e->d_enc, sizeof(EncState),
+					       offsetof(EncState, a) + offsetof(EncAna, par), par, (uint32_t *) d_qpar,
 					       d_act, e->channels, s));
+	else if (which == 1)
+		HIPCHK((hipError_t) kl_par_tap((const char *) e->d_dec, sizeof(DecState), offsetof(DecState, par), par,
+					       nullptr, d_act, e->channels, s));
 	else
-		HIPCHK((hipError_t) kl_parse(e->d_dec, d_par, (const uint8_t *) d_bits, d_act, e->channels, s));
+		HIPCHK((hipError_t) kl_parse(e->d_dec, par, (const uint8_t *) d_bits, d_act, e->channels, s));
 	return 0;
 }
 
@@ -2267,9 +2126,9 @@ int melpe_debug_encode_stage(melpe_engine *e, void *d_sp, int upto)
 int melpe_prof_read(uint64_t *out, int n)
 {
 	uint64_t acc[MELPE_PROF_SLOTS_ABI] = {0};
-	int (*rd[])(uint64_t *) = {melpe_tu_eng_prof, melpe_tu_npp_prof, melpe_tu_ana_prof, melpe_tu_anamw_prof,
-				   melpe_tu_harm_prof,
-				   melpe_tu_dec_prof, melpe_tu_r24_prof};
+#define TU_PROF(name) melpe_tu_##name##_prof,
+	int (*rd[])(uint64_t *) = {MELPE_TU_LIST(TU_PROF)};
+#undef TU_PROF
 	for (auto f : rd)
 		if (f(acc))
 			return fail_msg("not a profiling build (-DMELPE_PROF)");
@@ -2649,8 +2508,8 @@ int melpe_link_tx_dev(void *d_state, void *d_pkts, const void *d_voiced, void *d
 {
 	if (int rc = link_args("melpe_link_tx_dev", d_state, d_pkts, d_ret, channels, packets, true))
 		return rc;
-	if (int rc = kl_link_tx(d_state, d_pkts, d_voiced, d_ret, d_active, channels, packets,
-				(hipStream_t) hip_stream))
+	if (int rc = kl_link_tx((LinkState *) d_state, (uint8_t *) d_pkts, (const uint8_t *) d_voiced, (int32_t *) d_ret,
+				(const uint8_t *) d_active, channels, packets, (hipStream_t) hip_stream))
 		return fail("melpe_link_tx_dev", (hipError_t) rc);
 	return 0;
 }
@@ -2660,8 +2519,8 @@ int melpe_link_rx_dev(void *d_state, void *d_pkts, void *d_ret, void *d_voice, i
 {
 	if (int rc = link_args("melpe_link_rx_dev", d_state, d_pkts, d_ret, channels, packets, true))
 		return rc;
-	if (int rc = kl_link_rx(d_state, d_pkts, d_ret, d_voice, d_active, channels, packets,
-				(hipStream_t) hip_stream))
+	if (int rc = kl_link_rx((LinkState *) d_state, (uint8_t *) d_pkts, (int32_t *) d_ret, (uint8_t *) d_voice,
+				(const uint8_t *) d_active, channels, packets, (hipStream_t) hip_stream))
 		return fail("melpe_link_rx_dev", (hipError_t) rc);
 	return 0;
 }
@@ -2706,7 +2565,7 @@ int melpe_golay_sweep_dev(void *d_enc, void *d_digest, void *hip_stream)
 		return fail_msg("melpe_golay_sweep_dev: null argument");
 	if (((uintptr_t) d_enc & 3) || ((uintptr_t) d_digest & 7))
 		return fail_msg("melpe_golay_sweep_dev: misaligned argument");
-	if (int rc = kl_golay_sweep(d_enc, d_digest, (hipStream_t) hip_stream))
+	if (int rc = kl_golay_sweep((uint32_t *) d_enc, (uint64_t *) d_digest, (hipStream_t) hip_stream))
 		return fail("melpe_golay_sweep_dev", (hipError_t) rc);
 	return 0;
 }

@@ -4,7 +4,6 @@
  * the quantisers and channel packing, one lane per channel, reading the
  * NPP output k_enc_npp left in the caller's PCM.
  */
-#include <stdlib.h>
 #define MELPE_PROG_PRIO	/* progprio.h: ANA_CKPT */
 #include "kern.h"
 
@@ -18,10 +17,6 @@ struct AnaLane {
 	int16_t x[BLOCK];
 };
 
-/* MODE 0: the whole analysis and the bits here (MELPE_HARM=0).
- * MODE 1: the split form (encoder.h analysis_a): the windowed residuals to
- *         res (NF x LPC_FRAME per channel), the Fourier magnitudes and the
- *         packing in k_harm.hip. */
 #if defined(MELPE_WAVE_TIMES)
 /* diagnostics (tools/wave_times.py): each wave's start and end on the
  * chip-wide 100 MHz counter, to see how the launch's waves finish */
@@ -51,11 +46,17 @@ extern "C" int kl_wave_hw(unsigned *out, int n)
 #define WT_END() (void) 0
 #endif
 
+/* The split form of the analysis (encoder.h analysis_a): the windowed
+ * residuals to res (NF x LPC_FRAME per channel); the Fourier magnitudes and
+ * the packing, which writes the bits, are in k_harm.hip.
+ * MODE is a name tag only: the profiles and the tools that read them key on
+ * the symbol k_enc_ana<1>.  `bits` is unused and keeps the argument layout. */
 template <int MODE>
 __global__ __launch_bounds__(WAVE, MELPE_ENC_WAVES) void k_enc_ana(EncState *enc, const int16_t *sp, uint8_t *bits,
 						  const uint8_t *active, int n, const int *perm,
 						  const int *nlive, int16_t *res, AnaGate gate, int prio)
 {
+	static_assert(MODE == 1, "the unsplit analysis (MODE 0) is gone");
 	/* lane g runs channel perm[g] when the engine ordered the live channels
 	 * by pitch class (engine.hip, MELPE_BIN), else channel g under the mask;
 	 * the whole launch stands down unless the live count is the gate's
@@ -84,14 +85,8 @@ __global__ __launch_bounds__(WAVE, MELPE_ENC_WAVES) void k_enc_ana(EncState *enc
 	static_assert(offsetof(AnaLane, S) % 16 == 0, "the record copy is in 16-byte pieces");
 	lane_copy_x4(&L.S, &enc[c].a, nb);
 	lane_copy(L.x, sp + (size_t) c * BLOCK, sizeof(int16_t) * BLOCK);
-	if (MODE == 0)
-		analysis(&L.S, L.x);
-	else
-		analysis_a(&L.S, L.x, res + (size_t) c * NF * LPC_FRAME);
+	analysis_a(&L.S, L.x, res + (size_t) c * NF * LPC_FRAME);
 	lane_copy_x4(&enc[c].a, &L.S, nb);
-	if (MODE == 0)
-		for (int k = 0; k < 11; k++)
-			bits[(size_t) c * 11 + k] = L.S.chbuf[k];
 	WT_END();
 }
 
@@ -110,40 +105,26 @@ __global__ __launch_bounds__(WAVE, MELPE_ENC_WAVES) void k_enc_ana_dbg(EncState 
 	lane_copy(&enc[c].a, &L.S, ENC_ANA_LIVE);
 }
 
-/* MELPE_ANA_LDS (diagnostic): reserve that many bytes of LDS per wave to cap
- * the resident waves per CU (occupancy experiments) */
-static unsigned ana_lds_bytes(void)
-{
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MELPE_ANA_LDS");
-		v = e ? atoi(e) : 0;
-	}
-	return (unsigned) v;
-}
-
 /* MELPE_ANA_PRIO=0: no progress-driven priority (progprio.h), for A/Bs */
 static int ana_prio_mode(void)
 {
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MELPE_ANA_PRIO");
-		v = e ? (atoi(e) != 0) : 1;
-	}
+	static const int v = env_int("MELPE_ANA_PRIO", 1) != 0;
 	return v;
 }
 
-extern "C" int kl_enc_ana(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active,
-			  int n, const int *perm, const int *nlive, int16_t *res, AnaGate gate, hipStream_t s)
+/* the launch of k_enc_ana<1>, a lane per channel over `lanes` channels: the
+ * real one (n = lanes) and the warm-up (n = 0: every lane exits at once) */
+static int launch_ana(int lanes, EncState *enc, const int16_t *sp, const uint8_t *active, int n, const int *perm,
+		      const int *nlive, int16_t *res, AnaGate gate, int prio, hipStream_t s)
 {
-	const int pm = ana_prio_mode();
-	if (res)
-		k_enc_ana<1><<<grid_for(n), WAVE, ana_lds_bytes(), s>>>(enc, sp, bits, active, n, perm, nlive, res,
-									 gate, pm);
-	else
-		k_enc_ana<0><<<grid_for(n), WAVE, ana_lds_bytes(), s>>>(enc, sp, bits, active, n, perm, nlive, res,
-									 gate, pm);
+	k_enc_ana<1><<<grid_for(lanes), WAVE, 0, s>>>(enc, sp, nullptr, active, n, perm, nlive, res, gate, prio);
 	return (int) hipGetLastError();
+}
+
+extern "C" int kl_enc_ana(EncState *enc, const int16_t *sp, const uint8_t *active, int n, const int *perm,
+			  const int *nlive, int16_t *res, AnaGate gate, hipStream_t s)
+{
+	return launch_ana(n, enc, sp, active, n, perm, nlive, res, gate, ana_prio_mode(), s);
 }
 
 extern "C" int kl_enc_ana_dbg(EncState *enc, const int16_t *sp, int n, int upto, hipStream_t s)
@@ -152,21 +133,15 @@ extern "C" int kl_enc_ana_dbg(EncState *enc, const int16_t *sp, int n, int upto,
 	return (int) hipGetLastError();
 }
 
-/* the grid of a launch over n channels with no live channel (every lane
- * exits at once): the runtime still reserves the private-segment scratch
- * such a launch needs (engine.hip engine_reserve) */
-/* private-segment bytes per lane of the kernel (engine.hip engine_reserve) */
+/* the larger of the two analysis kernels: melpe_debug_encode_stage runs
+ * k_enc_ana_dbg on the engine stream too, and its frame is the larger */
 extern "C" size_t kl_ana_private(void)
 {
-	hipFuncAttributes a, b;	/* both forms: MELPE_HARM=0 runs k_enc_ana<0> */
-	size_t x = hipFuncGetAttributes(&a, (const void *) k_enc_ana<1>) == hipSuccess ? a.localSizeBytes : 0;
-	size_t y = hipFuncGetAttributes(&b, (const void *) k_enc_ana<0>) == hipSuccess ? b.localSizeBytes : 0;
+	const size_t x = private_bytes((const void *) k_enc_ana<1>), y = private_bytes((const void *) k_enc_ana_dbg);
 	return x > y ? x : y;
 }
 
 extern "C" int kl_ana_warm(int n, hipStream_t s)
 {
-	k_enc_ana<1><<<grid_for(n), WAVE, 0, s>>>(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr,
-						 AnaGate{}, 0);
-	return (int) hipGetLastError();
+	return launch_ana(n, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, AnaGate{}, 0, s);
 }

@@ -160,29 +160,30 @@ extern "C" size_t kl_enc_ana_mw_lq_words(int n)
 	return (size_t) LQ_ROW * mw_grid(n) * WAVE;
 }
 
-extern "C" int kl_enc_ana_mw(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active,
-			     int n, const int *perm, const int *nlive, int nw, uint32_t *lqbuf,
-			     AnaGate gate, hipStream_t s)
+/* the launch of k_enc_ana_mw over `slots` channels: the real one (n = slots)
+ * and the warm-up (n = 0: no group to run).  4 waves per 64 channels (2
+ * measured no better at any channel count and cost a third more compile
+ * time; ana_mw.h supports any count) */
+static int launch_ana_mw(int slots, EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active, int n,
+			 const int *perm, const int *nlive, uint32_t *lqbuf, AnaGate gate, hipStream_t s)
 {
-	/* 4 waves per 64 channels (2 measured no better at any channel count
-	 * and cost a third more compile time; ana_mw.h supports any count) */
-	if (nw == 4)
-		k_enc_ana_mw<4><<<mw_grid(n), WAVE * 4, 0, s>>>(enc, sp, bits, active, n, perm, nlive, lqbuf,
-								gate);
-	else
-		return (int) hipErrorInvalidValue;
+	k_enc_ana_mw<4><<<mw_grid(slots), WAVE * 4, 0, s>>>(enc, sp, bits, active, n, perm, nlive, lqbuf, gate);
 	return (int) hipGetLastError();
+}
+
+extern "C" int kl_enc_ana_mw(EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active,
+			     int n, const int *perm, const int *nlive, uint32_t *lqbuf, AnaGate gate,
+			     hipStream_t s)
+{
+	return launch_ana_mw(n, enc, sp, bits, active, n, perm, nlive, lqbuf, gate, s);
 }
 
 extern "C" size_t kl_ana_mw_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_enc_ana_mw<4>) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_enc_ana_mw<4>);
 }
 
 extern "C" int kl_ana_mw_warm(int n, hipStream_t s)
 {
-	k_enc_ana_mw<4><<<mw_grid(n), WAVE * 4, 0, s>>>(nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-							nullptr, AnaGate{});
-	return (int) hipGetLastError();
+	return launch_ana_mw(n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, AnaGate{}, s);
 }

@@ -4,13 +4,12 @@
  */
 #define MELPE_IDFT_LDS	/* realIDFT's table from LDS (decoder.h) */
 #define MELPE_PROG_PRIO	/* progprio.h: DEC_CKPT in k_decode */
-#include <stdlib.h>
 #include "kern.h"
 
 MELPE_TU(dec)
 
 /* up to four waves per block share one LDS copy of the realIDFT table;
- * kl_decode picks the widest block that still gives every CU four blocks */
+ * launch_decode picks the widest block that still gives every CU four blocks */
 #define DEC_BLOCK 256
 
 struct DecLane {
@@ -56,23 +55,28 @@ __global__ __launch_bounds__(DEC_BLOCK, MELPE_DEC_WAVES) void k_decode(DecState 
 /* MELPE_DEC_PRIO=0: no progress-driven priority (progprio.h), for A/Bs */
 static int dec_prio_mode(void)
 {
-	static int v = -1;
-	if (v < 0) {
-		const char *e = getenv("MELPE_DEC_PRIO");
-		v = e ? (atoi(e) != 0) : 1;
-	}
+	static const int v = env_int("MELPE_DEC_PRIO", 1) != 0;
 	return v;
+}
+
+/* the launch of k_decode, a lane per channel over `lanes` channels in the
+ * widest block that still gives every CU four blocks: the real one
+ * (n = lanes) and the warm-up (n = 0: every lane exits at once) */
+static int launch_decode(int lanes, DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
+			 const int *perm, const int *nlive, int prio, hipStream_t s)
+{
+	int b = DEC_BLOCK;
+	while (b > WAVE && (lanes + b - 1) / b < 1024)
+		b /= 2;
+	k_decode<<<(lanes + b - 1) / b, b, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(dec, sp, bits, active, n, perm,
+										 nlive, prio);
+	return (int) hipGetLastError();
 }
 
 extern "C" int kl_decode(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active,
 			 int n, const int *perm, const int *nlive, hipStream_t s)
 {
-	int b = DEC_BLOCK;
-	while (b > WAVE && (n + b - 1) / b < 1024)
-		b /= 2;
-	k_decode<<<(n + b - 1) / b, b, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(dec, sp, bits, active, n, perm, nlive,
-									     dec_prio_mode());
-	return (int) hipGetLastError();
+	return launch_decode(n, dec, sp, bits, active, n, perm, nlive, dec_prio_mode(), s);
 }
 
 /*
@@ -163,41 +167,40 @@ extern "C" size_t kl_decode2_hb_words(int n)
 	return (size_t) dec2_grid(n) * DEC2_GROUPS * 2 * HB_WORDS * WAVE;
 }
 
+/* the launch of k_decode2 over `slots` channels: the real one (n = slots)
+ * and the warm-up (n = 0: no lane is live) */
+static int launch_decode2(int slots, DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
+			  const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s)
+{
+	k_decode2<<<dec2_grid(slots), DEC2_BLOCK, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(dec, sp, bits, active, n,
+											 perm, nlive, hbuf);
+	return (int) hipGetLastError();
+}
+
 extern "C" int kl_decode2(DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
 			  const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s)
 {
 	if (n <= 0)
 		return 0;
-	k_decode2<<<dec2_grid(n), DEC2_BLOCK, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(dec, sp, bits, active, n,
-										     perm, nlive, hbuf);
-	return (int) hipGetLastError();
+	return launch_decode2(n, dec, sp, bits, active, n, perm, nlive, hbuf, s);
 }
 
 extern "C" size_t kl_dec2_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_decode2) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_decode2);
 }
 
 extern "C" int kl_dec2_warm(int n, hipStream_t s)
 {
-	k_decode2<<<dec2_grid(n), DEC2_BLOCK, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(
-		nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
-	return (int) hipGetLastError();
+	return launch_decode2(n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, s);
 }
 
 extern "C" size_t kl_dec_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_decode) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_decode);
 }
 
 extern "C" int kl_dec_warm(int n, hipStream_t s)
 {
-	int b = DEC_BLOCK;
-	while (b > WAVE && (n + b - 1) / b < 1024)
-		b /= 2;
-	k_decode<<<(n + b - 1) / b, b, IDFT_LDS_WORDS * sizeof(int16_t), s>>>(nullptr, nullptr, nullptr, nullptr,
-									     0, nullptr, nullptr, 0);
-	return (int) hipGetLastError();
+	return launch_decode(n, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, 0, s);
 }

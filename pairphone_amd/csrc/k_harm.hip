@@ -138,8 +138,8 @@ MD void wv_find_harm(const int16_t v[4], int16_t *fsmag, Word16 pitch, uint32_t 
 	wsync();
 }
 
-/* the windowed residuals k_enc_ana (mode 1) left in res */
-/* one wave per live channel: slot g runs channel perm[g] (the engine's
+/* the windowed residuals k_enc_ana left in res;
+ * one wave per live channel: slot g runs channel perm[g] (the engine's
  * lane order) or channel g under the mask; the three frames in order */
 __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t *res,
 						   const uint8_t *active, int n, const int *perm,
@@ -177,11 +177,19 @@ __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t 
 	}
 }
 
+/* the launch of k_enc_harm, a wave per channel over `waves` channels: the
+ * real one (n = waves) and the warm-up (n = 0: every wave exits at once) */
+static int launch_harm(int waves, EncState *enc, const int16_t *res, const uint8_t *active, int n,
+		       const int *perm, const int *nlive, AnaGate gate, hipStream_t s)
+{
+	k_enc_harm<<<waves, WAVE, 0, s>>>(enc, res, active, n, perm, nlive, gate);
+	return (int) hipGetLastError();
+}
+
 extern "C" int kl_enc_harm(EncState *enc, const int16_t *res, const uint8_t *active, int n,
 			   const int *perm, const int *nlive, AnaGate gate, hipStream_t s)
 {
-	k_enc_harm<<<n, WAVE, 0, s>>>(enc, res, active, n, perm, nlive, gate);
-	return (int) hipGetLastError();
+	return launch_harm(n, enc, res, active, n, perm, nlive, gate, s);
 }
 
 /* the superframe's packing after the magnitudes (analysis_b), lane per
@@ -221,31 +229,36 @@ __global__ __launch_bounds__(WAVE, 4) void k_enc_tail(EncState *enc, uint8_t *bi
 		bits[(size_t) c * 11 + k] = L.S.chbuf[k];
 }
 
+/* the launch of k_enc_tail, a lane per channel over `lanes` channels (real:
+ * n = lanes; warm-up: n = 0) */
+static int launch_tail(int lanes, EncState *enc, uint8_t *bits, const uint8_t *active, int n,
+		       const int *perm, const int *nlive, AnaGate gate, hipStream_t s)
+{
+	k_enc_tail<<<grid_for(lanes), WAVE, 0, s>>>(enc, bits, active, n, perm, nlive, gate);
+	return (int) hipGetLastError();
+}
+
 extern "C" int kl_enc_tail(EncState *enc, uint8_t *bits, const uint8_t *active, int n,
 			   const int *perm, const int *nlive, AnaGate gate, hipStream_t s)
 {
-	k_enc_tail<<<grid_for(n), WAVE, 0, s>>>(enc, bits, active, n, perm, nlive, gate);
-	return (int) hipGetLastError();
+	return launch_tail(n, enc, bits, active, n, perm, nlive, gate, s);
 }
 
 extern "C" size_t kl_harm_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_enc_tail) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_enc_tail);
 }
 
-/* private-segment bytes per lane of k_enc_harm (one wave per channel) */
 extern "C" size_t kl_harm_wave_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_enc_harm) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_enc_harm);
 }
 
 extern "C" int kl_harm_warm(int n, hipStream_t s)
 {
-	k_enc_harm<<<n, WAVE, 0, s>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{});
-	k_enc_tail<<<grid_for(n), WAVE, 0, s>>>(nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{});
-	return (int) hipGetLastError();
+	if (int rc = launch_harm(n, nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{}, s))
+		return rc;
+	return launch_tail(n, nullptr, nullptr, nullptr, 0, nullptr, nullptr, AnaGate{}, s);
 }
 
 /* Function-level parity test (dsp_eval_modes.h, wave mode wv_find_harm): one

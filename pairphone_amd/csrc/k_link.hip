@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "link.h"
+#include "launch.h"
 
 typedef uint32_t u32_may_alias __attribute__((__may_alias__));
 
@@ -250,29 +251,24 @@ __global__ __launch_bounds__(256) void k_golay_sweep(uint32_t *enc, uint64_t *di
 		digest[b] = part[0];
 }
 
-extern "C" int kl_link_tx(void *st, void *pkts, const void *voiced, void *ret, const void *active,
-			  int channels, int packets, hipStream_t s)
+extern "C" int kl_link_tx(LinkState *st, uint8_t *pkts, const uint8_t *voiced, int32_t *ret,
+			  const uint8_t *active, int channels, int packets, hipStream_t s)
 {
 	const size_t n = (size_t) channels * packets;
-	k_link_tx<<<(unsigned) ((n + TXB - 1) / TXB), TXB, 0, s>>>(
-		(const LinkState *) st, (uint8_t *) pkts, (const uint8_t *) voiced, (int32_t *) ret,
-		(const uint8_t *) active, channels, packets);
-	k_link_tx_state<<<(unsigned) ((channels + 63) / 64), 64, 0, s>>>(
-		(LinkState *) st, (const uint8_t *) active, channels, packets);
+	k_link_tx<<<(unsigned) ((n + TXB - 1) / TXB), TXB, 0, s>>>(st, pkts, voiced, ret, active, channels, packets);
+	k_link_tx_state<<<(unsigned) ((channels + 63) / 64), 64, 0, s>>>(st, active, channels, packets);
 	return (int) hipGetLastError();
 }
 
-extern "C" int kl_link_rx(void *st, void *pkts, void *ret, void *voice, const void *active, int channels,
-			  int packets, hipStream_t s)
+extern "C" int kl_link_rx(LinkState *st, uint8_t *pkts, int32_t *ret, uint8_t *voice, const uint8_t *active,
+			  int channels, int packets, hipStream_t s)
 {
-	k_link_rx<<<(unsigned) ((channels + 63) / 64), 64, 0, s>>>(
-		(LinkState *) st, (uint8_t *) pkts, (int32_t *) ret, (uint8_t *) voice, (const uint8_t *) active,
-		channels, packets);
+	k_link_rx<<<(unsigned) ((channels + 63) / 64), 64, 0, s>>>(st, pkts, ret, voice, active, channels, packets);
 	return (int) hipGetLastError();
 }
 
-extern "C" int kl_golay_sweep(void *enc, void *digest, hipStream_t s)
+extern "C" int kl_golay_sweep(uint32_t *enc, uint64_t *digest, hipStream_t s)
 {
-	k_golay_sweep<<<256, 256, 0, s>>>((uint32_t *) enc, (uint64_t *) digest);
+	k_golay_sweep<<<256, 256, 0, s>>>(enc, digest);
 	return (int) hipGetLastError();
 }

@@ -115,26 +115,29 @@ extern "C" int kl_npp(EncState *enc, int16_t *sp, int frames, int stride, const 
 	return (int) hipGetLastError();
 }
 
-extern "C" int kl_enc_npp(EncState *enc, int16_t *sp, const uint8_t *active, int n, hipStream_t s)
+/* the launch of k_enc_npp, a wave per channel over `waves` channels: the
+ * real one (n = waves) and the warm-up (n = 0: every wave exits at once) */
+static int launch_enc_npp(int waves, EncState *enc, int16_t *sp, const uint8_t *active, int n, hipStream_t s)
 {
-	k_enc_npp<<<npp_grid(n), NPP_WG, NPP_LDS_DYN, s>>>(enc, sp, active, n);
+	k_enc_npp<<<npp_grid(waves), NPP_WG, NPP_LDS_DYN, s>>>(enc, sp, active, n);
 	return (int) hipGetLastError();
 }
 
-/* private-segment bytes per lane of the wave-per-channel NPP kernels
- * (engine.hip engine_reserve) */
+extern "C" int kl_enc_npp(EncState *enc, int16_t *sp, const uint8_t *active, int n, hipStream_t s)
+{
+	return launch_enc_npp(n, enc, sp, active, n, s);
+}
+
+/* the larger of the two wave-per-channel NPP kernels */
 extern "C" size_t kl_npp_private(void)
 {
-	hipFuncAttributes a, b;
-	size_t x = hipFuncGetAttributes(&a, (const void *) k_enc_npp) == hipSuccess ? a.localSizeBytes : 0;
-	size_t y = hipFuncGetAttributes(&b, (const void *) k_npp) == hipSuccess ? b.localSizeBytes : 0;
+	const size_t x = private_bytes((const void *) k_enc_npp), y = private_bytes((const void *) k_npp);
 	return x > y ? x : y;
 }
 
 extern "C" int kl_npp_warm(int n, hipStream_t s)
 {
-	k_enc_npp<<<npp_grid(n), NPP_WG, NPP_LDS_DYN, s>>>(nullptr, nullptr, nullptr, 0);
-	return (int) hipGetLastError();
+	return launch_enc_npp(n, nullptr, nullptr, nullptr, 0, s);
 }
 
 /* Function-level parity test (dsp_eval.h), the forms that live in this TU.

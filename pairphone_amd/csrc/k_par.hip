@@ -59,14 +59,14 @@ __global__ __launch_bounds__(TAP_BLOCK) void k_par_tap(const char *rec, size_t s
 		qpar[c * QPAR_DW + (d - PAR_DW)] = v;
 }
 
-extern "C" int kl_par_tap(const void *rec, size_t stride, size_t off, void *par, void *qpar,
+extern "C" int kl_par_tap(const char *rec, size_t stride, size_t off, uint32_t *par, uint32_t *qpar,
 			  const uint8_t *active, int n, hipStream_t s)
 {
 	if (n <= 0)
 		return 0;
 	const size_t threads = (size_t) n * TAP_DW;
-	k_par_tap<<<(unsigned) ((threads + TAP_BLOCK - 1) / TAP_BLOCK), TAP_BLOCK, 0, s>>>(
-		(const char *) rec, stride, off, (uint32_t *) par, (uint32_t *) qpar, active, n);
+	k_par_tap<<<(unsigned) ((threads + TAP_BLOCK - 1) / TAP_BLOCK), TAP_BLOCK, 0, s>>>(rec, stride, off, par, qpar,
+											   active, n);
 	return (int) hipGetLastError();
 }
 
@@ -121,17 +121,16 @@ __global__ __launch_bounds__(WAVE) void k_parse(DecState *dec, uint32_t *par, co
 	}
 }
 
-extern "C" int kl_parse(DecState *dec, void *par, const uint8_t *bits, const uint8_t *active, int n,
+extern "C" int kl_parse(DecState *dec, uint32_t *par, const uint8_t *bits, const uint8_t *active, int n,
 			hipStream_t s)
 {
 	if (n <= 0)
 		return 0;
-	k_parse<<<grid_for(n), WAVE, 0, s>>>(dec, (uint32_t *) par, bits, active, n);
+	k_parse<<<grid_for(n), WAVE, 0, s>>>(dec, par, bits, active, n);
 	return (int) hipGetLastError();
 }
 
 extern "C" size_t kl_parse_private(void)
 {
-	hipFuncAttributes a;
-	return hipFuncGetAttributes(&a, (const void *) k_parse) == hipSuccess ? a.localSizeBytes : 0;
+	return private_bytes((const void *) k_parse);
 }

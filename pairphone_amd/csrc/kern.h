@@ -1,13 +1,16 @@
 /*
- * kern.h -- shared by the kernel translation units (k_npp.hip, k_ana.hip,
- * k_dec.hip, engine.hip).
+ * kern.h -- shared by the translation units that carry the codec: engine.hip,
+ * k_npp.hip, k_ana.hip, k_ana_mw.hip, k_harm.hip, k_dec.hip, k_r24.hip,
+ * k_dsp_eval.hip and k_par.hip (k_link.hip has no codec tables and includes
+ * only launch.h).
  *
  * Each TU is compiled separately (in parallel) into its own code object, so
  * each has its own copy of the constant tables (g_tab, g_der: tables.h) and
  * exports an upload function, MELPE_TU(name) -> melpe_tu_<name>_upload(),
  * that engine.hip calls once per device.  Kernels are launched through
  * extern "C" wrappers defined next to them (a kernel can only be launched
- * from its own TU without relocatable device code).
+ * from its own TU without relocatable device code).  launch.h declares the
+ * uploads and the wrappers, once, for both sides, and lists the TUs.
  *
  * Execution model: one lane per channel.  A kernel copies the
  * part of the channel's state it uses from its HBM record into the lane's
@@ -22,8 +25,10 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
+#include "launch.h"
 #include "progprio.h"	/* before the codec: its checkpoint hooks */
 #include "codec.h"
 
@@ -164,5 +169,19 @@ static inline unsigned grid_for(int n)
 	return (unsigned) ((n + WAVE - 1) / WAVE);
 }
 
+/* private-segment bytes per lane of a kernel (engine.hip engine_reserve) */
+static inline size_t private_bytes(const void *kernel)
+{
+	hipFuncAttributes a;
+	return hipFuncGetAttributes(&a, kernel) == hipSuccess ? a.localSizeBytes : 0;
+}
+
+/* an integer switch from the environment; a call site reads it once, into a
+ * static */
+static inline int env_int(const char *name, int def)
+{
+	const char *s = getenv(name);
+	return s ? atoi(s) : def;
+}
 
 #endif

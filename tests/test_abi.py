@@ -39,6 +39,25 @@ def test_no_oracle_in_product():
     assert "hostemu" not in deps and "ref_" not in deps
 
 
+def test_table_carrying_tus_listed_once():
+    """every translation unit that defines its table upload with
+    MELPE_TU(name) is in launch.h's MELPE_TU_LIST, and nothing else is: the
+    engine uploads the tables to exactly the TUs of that list, and a TU
+    left out would run with all-zero tables"""
+    csrc = os.path.join(ROOT, "pairphone_amd", "csrc")
+    defined = []
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith(".hip"):
+            defined += re.findall(r"^MELPE_TU\((\w+)\)", open(os.path.join(csrc, f)).read(), re.M)
+    head = open(os.path.join(csrc, "launch.h")).read()
+    m = re.search(r"^#define MELPE_TU_LIST\(X\)(.*)$", head, re.M)
+    assert m, "launch.h has no MELPE_TU_LIST"
+    listed = re.findall(r"X\((\w+)\)", m.group(1))
+    assert len(defined) == len(set(defined)) and len(listed) == len(set(listed))
+    assert set(defined) == set(listed)
+    assert len(listed) >= 9
+
+
 def test_codec_kernels_have_no_flat_accesses():
     """the build-time guard (pairphone_amd/build.py check_no_flat): the
     codec kernels reach private memory only through scratch_ instructions,

@@ -2,7 +2,7 @@
 """Knockout builds of the lane analysis (diagnostics, never shipped):
 build/var/ko_<stage>.so = the product library with k_ana.hip recompiled
 under -DMELPE_KO_<STAGE> (encoder.h: the stage is skipped, so the output is
-wrong by construction).  tools/gpu_r04_ko.sh prices each stage on MI355X by
+wrong by construction).  Round 4 priced each stage on MI355X with them, by
 the kernel-time and PMC-traffic difference against the product build.
 
   python tools/build_ko.py bpvc pauto classify lsfvq pitchana gpitch analysis

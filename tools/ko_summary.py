@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Knockout table of the lane analysis (tools/gpu_r04_ko.sh output) ->
+"""Knockout table of the lane analysis (round 4's knockout runs: per variant
+a kernel trace and the PMC passes of tools/gpu_ko_pmc.sh) ->
 profiles/<name>.json: per variant the analysis launch's kernel time and,
 from the PMC passes, HBM bytes and wave stalls per k_enc_ana<1> launch;
 each stage's price = product build minus the build without it.

@@ -1,10 +1,11 @@
 """Phase profile of the multi-wave analysis kernel (diagnostics): runs the
-stage-timer build (libmelpe_amd_prof.so) with MELPE_ANA_NW waves per 64
-channels and prints, per phase, the wall time wave 0 saw (barrier
+stage-timer build (libmelpe_amd_prof.so) with `waves` waves per 64 channels
+(MelpeEngine.set_ana_waves: 4 the multi-wave kernel, 0 by channel count) and
+prints, per phase, the wall time wave 0 saw (barrier
 included) and each virtual wave's busy time, in wave-cycles per workgroup
 per superframe (k_ana.hip MW_SLOT).
 
-  MELPE_ANA_NW=4 python tools/mw_prof.py [channels] [superframes]
+  python tools/mw_prof.py [channels] [superframes] [waves]
 """
 import os
 import sys
@@ -21,13 +22,14 @@ PHASES = (["frame 0", "frame 1", "frame 2", "lsf prelude+step 0|bands2"]
           + ["sc_ana+pvq prelude", "pvq slices", "pvq finish..", "find_harm", "pack"])
 
 
-def main(C=32768, nsf=4):
+def main(C=32768, nsf=4, nw=4):
     import torch
     import bench
     from pairphone_amd import MelpeEngine, load_library
     lib = load_library()
     dev = torch.device("cuda", 0)
     eng = MelpeEngine(C)
+    eng.set_ana_waves(nw)
     s = torch.cuda.current_stream(dev).cuda_stream
     pcm = torch.empty((nsf + 2, C, 540), dtype=torch.int16, device=dev)
     bits = torch.empty((nsf + 2, C, 11), dtype=torch.uint8, device=dev)
@@ -45,8 +47,7 @@ def main(C=32768, nsf=4):
     v = np.zeros(256, np.uint64)
     lib.melpe_prof_read(v.ctypes.data, 256)
     wg = C // 64 * nsf
-    nw = int(os.environ.get("MELPE_ANA_NW", "0"))
-    print("k_enc_ana_mw, %d channels, MELPE_ANA_NW=%d, cycles per workgroup per superframe" % (C, nw))
+    print("k_enc_ana_mw, %d channels, %d waves per 64 channels, cycles per workgroup per superframe" % (C, nw))
     print("  %-16s %10s %10s %10s %10s %10s" % ("phase", "wall(w0)", "v0", "v1", "v2", "v3"))
     tot = 0
     for p, name in enumerate(PHASES):
