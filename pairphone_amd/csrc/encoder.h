@@ -532,22 +532,56 @@ MN void analysis_tail(EncAna *E)
 }
 
 /* analysis() in the split form of the lane-per-channel kernels (k_ana.hip
- * k_enc_ana, k_harm.hip): analysis_a runs everything before the Fourier
- * magnitudes, writes each voiced frame's windowed residual of the quantised
- * LSFs to res[i * LPC_FRAME ..] (melp_ana.c:224-233, the input of
- * find_harm; an unvoiced frame's row is not written) and does the history
- * shift; the magnitudes go into par[i].fs_mag (k_enc_harm), then
- * analysis_b packs the superframe.  The shift reads only hpspeech, which
- * nothing after it reads, so moving it ahead of the packing changes no
- * value. */
-MN void analysis_a2(EncAna *E, int16_t *res)
+ * k_enc_ana, k_quant.hip k_enc_quant, k_harm.hip):
+ * analysis_a1 runs the three frames and sc_ana, after which the caller does
+ * the history shift (ana_shift);
+ * analysis_q runs the quantisers and writes each voiced frame's windowed
+ * residual of the quantised LSFs to res[i * LPC_FRAME ..]
+ * (melp_ana.c:224-233, the input of find_harm; an unvoiced frame's row is
+ * not written);
+ * the magnitudes go into par[i].fs_mag (k_enc_harm), then analysis_b packs
+ * the superframe.
+ * The cut after sc_ana is where the superframe's voicing pattern becomes
+ * known: everything from lsf_vq on branches on it, so the engine sorts the
+ * lanes by it between the two kernels.  Of hpspeech analysis_q reads only
+ * the residual windows, [ANA_RES_BEG, ANA_RES_END), which are samples from
+ * before the shift: the caller hands that span over (its own frame keeps
+ * them at the same indices).  The shift reads only hpspeech and writes
+ * below the part it reads, so doing it ahead of the quantisers' kernel
+ * changes no value. */
+#define ANA_RES_BEG (FRAME_END - LPC_FRAME / 2 - LPC_ORD)	/* 140 */
+#define ANA_RES_END ((NF - 1) * FRAME + FRAME_END + LPC_FRAME / 2)	/* 710 */
+/* the span as the kernels move it, widened to 16-byte pieces of hpspeech; it
+ * fits the channel's NF x LPC_FRAME row of the residual buffer, which holds
+ * it until analysis_q's rows replace it */
+#define ANA_XSPAN_BEG (ANA_RES_BEG & ~7)
+#define ANA_XSPAN_END ((ANA_RES_END + 7) & ~7)
+#define ANA_XSPAN_BYTES (sizeof(int16_t) * (ANA_XSPAN_END - ANA_XSPAN_BEG))
+static_assert(ANA_XSPAN_END <= IN_BEG + BLOCK && ANA_XSPAN_END - ANA_XSPAN_BEG <= NF * LPC_FRAME,
+	      "the residual span lies in hpspeech and fits a row of the residual buffer");
+static_assert((sizeof(int16_t) * NF * LPC_FRAME) % 16 == 0, "rows of the residual buffer in 16-byte pieces");
+
+MN void analysis_a1(EncAna *E, const int16_t *sp_in)
 {
+#if defined(MELPE_KO_ANALYSIS)
+	return;
+#endif
+	for (int i = 0; i < NF; i++) {
+		analysis_frame(E, sp_in, i);
+		ANA_CKPT(i + 1);
+	}
+	sc_ana(E, E->par);
+}
+
+MN void analysis_q(EncAna *E, int16_t *res)
+{
+#if defined(MELPE_KO_ANALYSIS)
+	return;
+#endif
 	MelpParam *par = E->par;
-	sc_ana(E, par);
 #if !defined(MELPE_KO_LSFVQ)
 	lsf_vq(E, par);
 #endif
-	ANA_CKPT(4);
 	pitch_vq(E, par);
 	gain_vq(E, par);
 	for (int i = 0; i < NF; i++)
@@ -566,19 +600,6 @@ MN void analysis_a2(EncAna *E, int16_t *res)
 		window(E->sigbuf, TB(win_cof), E->sigbuf, LPC_FRAME);
 		v_copy(&res[i * LPC_FRAME], E->sigbuf, LPC_FRAME);
 	}
-	v_copy(E->hpspeech, &E->hpspeech[NF * FRAME], IN_BEG);
-}
-
-MN void analysis_a(EncAna *E, const int16_t *sp_in, int16_t *res)
-{
-#if defined(MELPE_KO_ANALYSIS)
-	return;
-#endif
-	for (int i = 0; i < NF; i++) {
-		analysis_frame(E, sp_in, i);
-		ANA_CKPT(i + 1);
-	}
-	analysis_a2(E, res);
 }
 
 /* the history shift at the end of analysis (melp_ana.c:262) */

@@ -681,6 +681,19 @@ __device__ __forceinline__ int bin_class(const char *rec, int off_par, int off_u
 	return nv * BIN_PITCHES + b;
 }
 
+/* The second lane order of the encoder (ana_launch): the class of a record
+ * is the voicing pattern of the superframe being encoded, the uv_flags of
+ * par[0..2] as k_enc_ana's sc_ana left them (quant.h lsf_uvc: frame 0 in bit
+ * 2), 8 classes.  lsf_vq, quant_fsmag and the residual loop branch on it. */
+#define KEY_PITCH 0	/* bin_class */
+#define KEY_VOICING 1	/* bin_class_uvc */
+__device__ __forceinline__ int bin_class_uvc(const char *rec, int off_par)
+{
+	const MelpParam *par = (const MelpParam *) (rec + off_par);
+	return (par[0].uv_flag ? 4 : 0) | (par[1].uv_flag ? 2 : 0) | (par[2].uv_flag ? 1 : 0);
+}
+
+template <int KEY>
 __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t stride, int off_par,
 						   int off_uv, const uint8_t *active, int n, BinBuf b)
 {
@@ -692,7 +705,8 @@ __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t strid
 	if (c < n) {
 		int k = NOT_LIVE;
 		if (!active || active[c]) {
-			k = bin_class(rec + (size_t) c * stride, off_par, off_uv);
+			k = KEY == KEY_VOICING ? bin_class_uvc(rec + (size_t) c * stride, off_par)
+					       : bin_class(rec + (size_t) c * stride, off_par, off_uv);
 			atomicAdd(&cnt[k], 1u);
 		}
 		b.key[c] = (uint16_t) k;
@@ -743,21 +757,38 @@ static bool bin_enabled(void)
 	return on;
 }
 
+/* the part of a sort that depends on no record: s waits for the kernel that
+ * read b's previous order when that ran on another stream, then the class
+ * counters are zeroed.  bin_launch does it itself unless told that the
+ * caller already has (ana_launch, for the second order: the zeroing is a
+ * dispatch of its own, and issued only after k_enc_ana it queued 2 ms behind
+ * the resident NPP and analysis waves, profiles/r07_new_kernel_stats.txt). */
+static hipError_t bin_prepare(BinBuf &b, hipStream_t s)
+{
+	hipError_t er;
+	if (b.used && b.last != s && (er = hipStreamWaitEvent(s, b.done, 0)) != hipSuccess)
+		return er;
+	return hipMemsetAsync(b.ctl, 0, sizeof(unsigned) * NBIN, s);
+}
+
 /* sorts the live channels of `rec` (records of `stride` bytes) into b.perm on
- * stream s; *on: whether the order is used (false: identity lanes + mask) */
+ * stream s by the class `key` gives them; *on: whether the order is used
+ * (false: identity lanes + mask) */
 static hipError_t bin_launch(int order, BinBuf &b, const void *rec, size_t stride, int off_par,
-			     int off_uv, const uint8_t *active, int n, hipStream_t s, bool *on)
+			     int off_uv, const uint8_t *active, int n, hipStream_t s, bool *on,
+			     int key = KEY_PITCH, bool prepared = false)
 {
 	*on = !(order == 0 || (order < 0 && !bin_enabled()));
 	if (!*on)
 		return hipSuccess;
 	hipError_t er;
-	if (b.used && b.last != s && (er = hipStreamWaitEvent(s, b.done, 0)) != hipSuccess)
+	if (!prepared && (er = bin_prepare(b, s)) != hipSuccess)
 		return er;
 	unsigned g = (unsigned) ((n + 255) / 256);
-	if ((er = hipMemsetAsync(b.ctl, 0, sizeof(unsigned) * NBIN, s)) != hipSuccess)
-		return er;
-	k_bin_count<<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
+	if (key == KEY_VOICING)
+		k_bin_count<KEY_VOICING><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
+	else
+		k_bin_count<KEY_PITCH><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
 	if ((er = hipGetLastError()) != hipSuccess)
 		return er;
 	k_bin_scan<<<1, WAVE, 0, s>>>(b);
@@ -799,6 +830,7 @@ struct melpe_engine {
 	uint8_t *d_mask = nullptr;
 	int16_t *d_npp = nullptr;	/* staging of melpe_npp_host, grown on demand */
 	BinBuf bin_enc, bin_dec;	/* pitch-class lane order of k_enc_ana / k_decode */
+	BinBuf bin_enc2;	/* voicing-pattern lane order of k_enc_quant / k_enc_harm / k_enc_tail */
 	int lane_order = -1;	/* 1 on, 0 off, -1 the MELPE_BIN default */
 	int ana_waves = 0;	/* waves per 64 channels in k_enc_ana(_mw); 0: by channel count */
 	uint32_t *d_lq = nullptr;	/* k_enc_ana_mw's lsf_vq score rows (engine_reserve) */
@@ -868,8 +900,6 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 				   d_act, e->channels, s, &on);
 	if (er != hipSuccess)
 		return (int) er;
-	if (after_sort && (er = hipEventRecord(after_sort, s)) != hipSuccess)
-		return (int) er;
 	const int *perm = on ? b.perm : nullptr;
 	const int *nlive = on ? (const int *) (b.ctl + 2 * NBIN) : nullptr;
 	int nw = ana_waves_for(e);
@@ -883,7 +913,24 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 	 * No host readback, so host run-ahead cannot make the choice stale.
 	 * Either mapping gives the same bits (the four-wave kernel grid-strides
 	 * over every live slot). */
-	const bool dual = nw == 1 && on && e->ana_waves == 0 && e->mw_live_max > 0;
+	bool dual = nw == 1 && on && e->ana_waves == 0 && e->mw_live_max > 0;
+	/* An engine small enough for the four-wave kernel alone takes the same
+	 * dual path once the caller has set the live count at which the lane
+	 * kernels take over below its channel count
+	 * (melpe_engine_set_mw_live_max; the default, MW_MAX_CHANNELS, never
+	 * is). */
+	if (nw == 4 && on && e->ana_waves == 0 && e->mw_live_max > 0 && e->mw_live_max < e->channels) {
+		dual = true;
+		nw = 1;
+	}
+	/* the second order's counters are zeroed here, beside the first sort
+	 * and ahead of after_sort, while the GPU is not yet full of the next
+	 * superframe's NPP */
+	BinBuf &b2 = e->bin_enc2;
+	if (on && nw == 1 && (er = bin_prepare(b2, s)) != hipSuccess)
+		return (int) er;
+	if (after_sort && (er = hipEventRecord(after_sort, s)) != hipSuccess)
+		return (int) er;
 	AnaGate lane = all, mw = all;
 	if (dual) {
 		lane.lo = e->mw_live_max;
@@ -893,14 +940,36 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 	if (dual || nw == 4)
 		rc = kl_enc_ana_mw(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_lq, mw, s);
 	if (rc == 0 && nw == 1) {
-		/* lane-per-channel analysis up to the Fourier magnitudes, the
-		 * magnitudes with a wave per channel, then the packing
-		 * (k_harm.hip) */
+		/* lane-per-channel analysis up to sc_ana (k_ana.hip), the
+		 * quantisers (k_quant.hip), the Fourier magnitudes with a wave per
+		 * channel, then the packing (k_harm.hip) */
 		rc = kl_enc_ana(e->d_enc, d_sp, d_act, e->channels, perm, nlive, e->d_res, lane, s);
+		/* The second lane order.  What follows sc_ana branches on the
+		 * superframe's voicing pattern (lsf_vq's codebooks and searches,
+		 * quant_fsmag, the residual loop), which the first order cannot
+		 * know: it sorts by the previous superframe, and this one's
+		 * pattern exists only once k_enc_ana has written par[].uv_flag.
+		 * So the live channels are sorted again here, by that pattern, and
+		 * the three kernels below run on this order.  The live count is
+		 * the first sort's (same mask), so the gate decides alike; when
+		 * the four-wave kernel ran, the sort is wasted and they stand
+		 * down. */
+		if (rc == 0 && on) {
+			bool on2;
+			rc = (int) bin_launch(1, b2, e->d_enc, sizeof(EncState),
+					      (int) (offsetof(EncState, a) + offsetof(EncAna, par)), 0, d_act,
+					      e->channels, s, &on2, KEY_VOICING, true);
+			perm = b2.perm;
+			nlive = (const int *) (b2.ctl + 2 * NBIN);
+		}
+		if (rc == 0)
+			rc = kl_enc_quant(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
 		if (rc == 0)
 			rc = kl_enc_harm(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
 		if (rc == 0)
 			rc = kl_enc_tail(e->d_enc, d_bits, d_act, e->channels, perm, nlive, lane, s);
+		if (rc == 0 && on)
+			rc = (int) bin_release(b2, s);
 	}
 	if (rc == 0 && on)
 		rc = (int) bin_release(b, s);
@@ -1269,7 +1338,7 @@ static int engine_streams(melpe_engine *e, bool dec)
  * on cin.  The NPP touches only the records' NppState and the next PCM, the
  * analysis only their EncAna and this PCM, the VAD its own state; the
  * encoder and decoder halves of a record and their lane-order buffers
- * (bin_enc, bin_dec) are disjoint.  The hop back to the caller covers all
+ * (bin_enc and bin_enc2, bin_dec) are disjoint.  The hop back to the caller covers all
  * three; melpe_last_kernel_ms reports the analysis.
  */
 struct PipeNext {	/* the next superframe, or none */
@@ -1345,7 +1414,8 @@ static int engine_warm(melpe_engine *e)
 {
 	hipError_t er;
 	const int mw = e->channels < MW_MAX_CHANNELS ? e->channels : MW_MAX_CHANNELS;
-	int (*warm[])(int, hipStream_t) = {kl_npp_warm, kl_ana_warm, kl_harm_warm, kl_ana_mw_warm, kl_dec_warm};
+	int (*warm[])(int, hipStream_t) = {kl_npp_warm, kl_ana_warm, kl_quant_warm, kl_harm_warm, kl_ana_mw_warm,
+						    kl_dec_warm};
 	for (auto f : warm)
 		if ((er = (hipError_t) f(f == kl_ana_mw_warm ? mw : e->channels, e->stream)) != hipSuccess)
 			return fail("melpe_engine: codec kernel scratch could not be reserved", er);
@@ -1384,7 +1454,9 @@ static int engine_reserve(melpe_engine *e)
 	 * most 512 groups; the wave-per-channel kernels k_enc_npp / k_npp and
 	 * k_enc_harm: one per channel, up to the device's resident waves). */
 	{
-		const size_t lane = kl_ana_private() > kl_harm_private() ? kl_ana_private() : kl_harm_private();
+		size_t lane = kl_ana_private() > kl_harm_private() ? kl_ana_private() : kl_harm_private();
+		if (kl_quant_private() > lane)
+			lane = kl_quant_private();
 		/* (k_parse's frame, the record's excitation side, is far below
 		 * the decoder's: it never sets the maximum and needs no warm-up) */
 		const size_t dec_lane = kl_dec_private() > kl_parse_private() ? kl_dec_private() : kl_parse_private();
@@ -1455,6 +1527,7 @@ int melpe_engine_create(melpe_engine **out, int device, int channels)
 	CREATE_STEP(hipMalloc(&e->d_mask, (size_t) channels));
 	CREATE_STEP(bin_alloc(&e->bin_enc, channels));
 	CREATE_STEP(bin_alloc(&e->bin_dec, channels));
+	CREATE_STEP(bin_alloc(&e->bin_enc2, channels));
 #undef CREATE_STEP
 	if (er != hipSuccess) {
 		int r = fail(what, er);
@@ -1566,6 +1639,7 @@ int melpe_engine_destroy(melpe_engine *e)
 	hipFree(e->d_mask);
 	hipFree(e->bin_enc.perm);
 	hipFree(e->bin_dec.perm);
+	hipFree(e->bin_enc2.perm);
 	hipFree(e->d_lq);
 	hipFree(e->d_hb);
 	hipFree(e->d_res);
@@ -1575,6 +1649,8 @@ int melpe_engine_destroy(melpe_engine *e)
 		hipEventDestroy(e->bin_enc.done);
 	if (e->bin_dec.done)
 		hipEventDestroy(e->bin_dec.done);
+	if (e->bin_enc2.done)
+		hipEventDestroy(e->bin_enc2.done);
 	if (e->ev0)
 		hipEventDestroy(e->ev0);
 	if (e->ev1)

@@ -114,24 +114,48 @@ int emu_encode_npp(emu_engine *e, int16_t *sp)
 	return 0;
 }
 
-/* the split lane analysis as k_enc_ana / k_enc_harm / k_enc_tail run it,
- * with the Fourier magnitudes from the scalar find_harm on the written
- * residuals (the wave kernel's own arithmetic is checked on the GPU) */
+/* the split lane analysis as k_enc_ana / k_enc_quant / k_enc_harm /
+ * k_enc_tail run it, each part on a frame of its own that holds what the
+ * kernel is handed and a pattern everywhere else, with the Fourier
+ * magnitudes from the scalar find_harm on the written residuals (the wave
+ * kernel's own arithmetic is checked on the GPU) */
 int emu_encode_ana_split(emu_engine *e, unsigned char *bits, const int16_t *sp)
 {
 	static int16_t res[NF * LPC_FRAME];
 	static EncAna L;	/* the lane's private copy (k_ana.hip AnaLane) */
+	static EncAna Q;	/* k_quant.hip QuantLane */
+	/* the record ranges k_enc_quant moves: par + qpar, pvq_prev_uv_flag ..
+	 * qplsp (the kernel widens the second to dwords; here it is exact) */
+	const size_t o = offsetof(EncAna, par), n = offsetof(EncAna, voicedEn) - o;
+	const size_t o2 = offsetof(EncAna, pvq_prev_uv_flag), n2 = offsetof(EncAna, fsm_prev_uv) - o2;
 	for (int c = 0; c < e->channels; c++) {
-		EncAna *E = &L;
+		EncAna *E = &L, *R = &e->enc[c].a;
+		/* k_enc_ana.  The live prefix in, the working storage a pattern
+		 * (state.h): nothing may read it before writing it */
+		memcpy(E, R, ENC_ANA_LIVE);
+		memset((char *) E + ENC_ANA_LIVE, 0x5a + (c & 7), sizeof(EncAna) - ENC_ANA_LIVE);
+		analysis_a1(E, sp + (size_t) c * BLOCK);
+		/* the residual span goes out through the channel's row of res,
+		 * whose tail it leaves alone */
+		for (int k = 0; k < NF * LPC_FRAME; k++)
+			res[k] = (int16_t) 0x5a5a;
+		memcpy(res, &E->hpspeech[ANA_RES_BEG], sizeof(int16_t) * (ANA_RES_END - ANA_RES_BEG));
+		ana_shift(E);
+		memcpy(R, E, ENC_ANA_LIVE);
+		/* k_enc_quant.  Its record ranges and the span in, the rest a
+		 * pattern; the span is taken whole before any row is written */
+		E = &Q;
+		memset(E, 0xa5 - (c & 7), sizeof(EncAna));
+		memcpy((char *) E + o, (const char *) R + o, n);
+		memcpy((char *) E + o2, (const char *) R + o2, n2);
+		memcpy(&E->hpspeech[ANA_RES_BEG], res, sizeof(int16_t) * (ANA_RES_END - ANA_RES_BEG));
 		for (int k = 0; k < NF * LPC_FRAME; k++)
 			res[k] = (int16_t) 0x5a5a;	/* unvoiced rows stay unread */
-		/* the live prefix in, the working storage a pattern (state.h):
-		 * nothing may read it before writing it */
-		memcpy(E, &e->enc[c].a, ENC_ANA_LIVE);
-		memset((char *) E + ENC_ANA_LIVE, 0x5a + (c & 7), sizeof(EncAna) - ENC_ANA_LIVE);
-		analysis_a(E, sp + (size_t) c * BLOCK, res);
-		memcpy(&e->enc[c].a, E, ENC_ANA_LIVE);
-		E = &e->enc[c].a;
+		analysis_q(E, res);
+		memcpy((char *) R + o, (const char *) E + o, n);
+		memcpy((char *) R + o2, (const char *) E + o2, n2);
+		/* k_enc_harm and k_enc_tail, on the record */
+		E = R;
 		for (int i = 0; i < NF; i++) {
 			MelpParam *par = &E->par[i];
 			v_set(par->fs_mag, 8192, NUM_HARM);

@@ -1,8 +1,9 @@
 /*
  * k_ana.hip -- the analysis half of melpe_a (melpe/melpe.c:97-98:
- * analysis() + the 11-byte frame): dc removal, melp_ana per frame, sc_ana,
- * the quantisers and channel packing, one lane per channel, reading the
- * NPP output k_enc_npp left in the caller's PCM.
+ * analysis() + the 11-byte frame): dc removal, melp_ana per frame and
+ * sc_ana, one lane per channel, reading the NPP output k_enc_npp left in the
+ * caller's PCM.  The quantisers are in k_quant.hip, the Fourier magnitudes
+ * and the channel packing in k_harm.hip.
  */
 #define MELPE_PROG_PRIO	/* progprio.h: ANA_CKPT */
 #include "kern.h"
@@ -46,9 +47,13 @@ extern "C" int kl_wave_hw(unsigned *out, int n)
 #define WT_END() (void) 0
 #endif
 
-/* The split form of the analysis (encoder.h analysis_a): the windowed
- * residuals to res (NF x LPC_FRAME per channel); the Fourier magnitudes and
- * the packing, which writes the bits, are in k_harm.hip.
+/* The split form of the analysis (encoder.h analysis_a1): the three frames
+ * and sc_ana.  The quantisers that follow branch on the voicing pattern
+ * sc_ana leaves, so they run in a kernel of their own (k_quant.hip) on waves
+ * sorted by that pattern; the residuals they make come from speech the
+ * history shift drops, so that span goes out to the channel's row of res
+ * first, from every lane alike.  The Fourier magnitudes and the packing,
+ * which writes the bits, are in k_harm.hip.
  * MODE is a name tag only: the profiles and the tools that read them key on
  * the symbol k_enc_ana<1>.  `bits` is unused and keeps the argument layout. */
 template <int MODE>
@@ -83,9 +88,13 @@ __global__ __launch_bounds__(WAVE, MELPE_ENC_WAVES) void k_enc_ana(EncState *enc
 	PIN_FRAME(L);
 	constexpr size_t nb = ENC_ANA_LIVE;
 	static_assert(offsetof(AnaLane, S) % 16 == 0, "the record copy is in 16-byte pieces");
+	static_assert((offsetof(AnaLane, S) + offsetof(EncAna, hpspeech) + sizeof(int16_t) * ANA_XSPAN_BEG) % 16 == 0,
+		      "and so is the span copy");
 	lane_copy_x4(&L.S, &enc[c].a, nb);
 	lane_copy(L.x, sp + (size_t) c * BLOCK, sizeof(int16_t) * BLOCK);
-	analysis_a(&L.S, L.x, res + (size_t) c * NF * LPC_FRAME);
+	analysis_a1(&L.S, L.x);
+	lane_copy_x4(res + (size_t) c * NF * LPC_FRAME, &L.S.hpspeech[ANA_XSPAN_BEG], ANA_XSPAN_BYTES);
+	ana_shift(&L.S);
 	lane_copy_x4(&enc[c].a, &L.S, nb);
 	WT_END();
 }

@@ -5,8 +5,8 @@
  *
  * In the lane-per-channel analysis each lane ran find_harm's 512-point real
  * FFT alone, 2 KB of private state per channel: 12% of k_enc_ana at
- * 262,144 channels.  Here k_enc_ana stops after writing each voiced frame's
- * windowed residual (analysis_a), k_enc_harm runs the FFT across the 64
+ * 262,144 channels.  Here k_enc_quant (k_quant.hip) leaves each voiced
+ * frame's windowed residual (analysis_q), k_enc_harm runs the FFT across the 64
  * lanes of a wave in LDS -- the NPP's wave FFT (npp_wave.h wv_cfft256: the
  * same fft_lib.c cfft, same per-stage guard scaling) plus rfft's split and
  * twiddle passes with one step per lane -- and the harmonic peak search, and
@@ -138,7 +138,7 @@ MD void wv_find_harm(const int16_t v[4], int16_t *fsmag, Word16 pitch, uint32_t 
 	wsync();
 }
 
-/* the windowed residuals k_enc_ana left in res;
+/* the windowed residuals k_enc_quant left in res;
  * one wave per live channel: slot g runs channel perm[g] (the engine's
  * lane order) or channel g under the mask; the three frames in order */
 __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t *res,

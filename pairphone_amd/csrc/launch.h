@@ -26,7 +26,7 @@ struct LinkState;
 /* the translation units that carry their own copy of the constant tables:
  * MELPE_TU(name) in the TU's .hip is the one definition site, this list the
  * one place that names them all (tests/test_abi.py holds the two equal) */
-#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(par)
+#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(quant) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(par)
 
 extern "C" {
 
@@ -43,10 +43,16 @@ int kl_enc_npp(mlp::EncState *enc, int16_t *sp, const uint8_t *active, int n, hi
 int kl_dsp_scalar_lds(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
 int kl_dsp_wave_fft(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
 
-/* k_ana.hip: the lane analysis up to the windowed residuals (res) */
+/* k_ana.hip: the lane analysis up to sc_ana; res receives the speech span
+ * the quantisers' residuals are made from */
 int kl_enc_ana(mlp::EncState *enc, const int16_t *sp, const uint8_t *active, int n, const int *perm,
 	       const int *nlive, int16_t *res, AnaGate gate, hipStream_t s);
 int kl_enc_ana_dbg(mlp::EncState *enc, const int16_t *sp, int n, int upto, hipStream_t s);
+
+/* k_quant.hip: the quantisers after sc_ana; res in (the span), out (each
+ * voiced frame's windowed residual) */
+int kl_enc_quant(mlp::EncState *enc, int16_t *res, const uint8_t *active, int n, const int *perm,
+		 const int *nlive, AnaGate gate, hipStream_t s);
 
 /* k_harm.hip */
 int kl_enc_harm(mlp::EncState *enc, const int16_t *res, const uint8_t *active, int n, const int *perm,
@@ -98,6 +104,7 @@ int kl_golay_sweep(uint32_t *enc, uint64_t *digest, hipStream_t s);
  * at once and the runtime reserves what the real launch will need. */
 size_t kl_npp_private(void);
 size_t kl_ana_private(void);
+size_t kl_quant_private(void);
 size_t kl_harm_private(void);	/* k_enc_tail, lane per channel */
 size_t kl_harm_wave_private(void);	/* k_enc_harm, wave per channel */
 size_t kl_ana_mw_private(void);
@@ -106,6 +113,7 @@ size_t kl_dec2_private(void);
 size_t kl_parse_private(void);
 int kl_npp_warm(int n, hipStream_t s);
 int kl_ana_warm(int n, hipStream_t s);
+int kl_quant_warm(int n, hipStream_t s);
 int kl_harm_warm(int n, hipStream_t s);
 int kl_ana_mw_warm(int n, hipStream_t s);
 int kl_dec_warm(int n, hipStream_t s);

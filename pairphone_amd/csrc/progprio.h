@@ -12,8 +12,10 @@
  * each SIMD -- took 19.4 ms and the last 24.6 ms; even data-independent
  * stages (lpc_acor) ran 37% slower in the last quarter, and inverting the
  * priority by quarter inverted the times.  So each wave counts the
- * checkpoints it passes (ANA_CKPT in encoder.h: after each frame and after
- * lsf_vq; DEC_CKPT in decoder.h: after each frame) on one counter per launch
+ * checkpoints it passes (ANA_CKPT in encoder.h: after each frame -- three
+ * since lsf_vq, which the fourth followed, left the kernel for k_enc_quant;
+ * the distance below is in checkpoints passed, so it needs no total --
+ * DEC_CKPT in decoder.h: after each frame) on one counter per launch
  * and sets its priority from how far it is behind the average.  The waves
  * then end together (profiles/r06_r_prio_wave_times.txt).  The four-wave
  * analysis (k_enc_ana_mw) measured neutral with a checkpoint every fourth

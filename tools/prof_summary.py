@@ -45,22 +45,30 @@ def kernel_stats(db):
 
 
 def pmc_means(db):
-    """mean counter values per dispatch of each kernel, leaving out each
-    kernel's first dispatch when it has more than one: melpe_engine_create
-    launches every codec kernel once at its full grid with no work (the
-    scratch reservation), and that launch would dilute the means"""
+    """mean counter values per dispatch of each kernel, leaving out the
+    dispatches without work: melpe_engine_create launches every codec kernel
+    once at its full grid with no live channel (the scratch reservation),
+    the bench creates an engine per leg, and those launches would dilute the
+    means.  One counter of the pass measures a kernel's work (its wave
+    cycles where the pass has them, else the counter with the largest
+    value), and a dispatch counts, with all its counters, when it reaches
+    10% of the kernel's largest value of that one: every mean and ratio of
+    a pass is then over the same dispatches.  (A kernel whose real launches
+    differ more than tenfold in one run would lose the small ones: profile
+    one channel count per run, as tools/gpu_pmc.sh does.)"""
     c = sqlite3.connect(db)
     per = collections.defaultdict(lambda: collections.defaultdict(float))
     for name, disp, cn, cv in c.execute(
             "select name,dispatch_id,counter_name,counter_value from pmc_events"):
         per[(short(name), disp)][cn] += cv
-    first = {}
-    for (k, disp) in per:
-        first[k] = min(first.get(k, disp), disp)
-    count = collections.Counter(k for (k, _) in per)
+    peak = collections.defaultdict(lambda: collections.defaultdict(float))
+    for (k, disp), v in per.items():
+        for cn, cv in v.items():
+            peak[k][cn] = max(peak[k][cn], cv)
+    work = {k: "SQ_WAVE_CYCLES" if "SQ_WAVE_CYCLES" in p else max(p, key=p.get) for k, p in peak.items()}
     agg = collections.defaultdict(lambda: collections.defaultdict(list))
     for (k, disp), v in per.items():
-        if count[k] > 1 and disp == first[k]:
+        if v.get(work[k], 0.0) * 10 < peak[k][work[k]]:
             continue
         for cn, cv in v.items():
             agg[k][cn].append(cv)
