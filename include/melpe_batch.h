@@ -111,7 +111,10 @@ int melpe_engine_set_dec_waves(melpe_engine *e, int waves);
  * needs the lane order on, the default), and the host never reads the
  * count.  live_max >= 0 (default 32,768, where the four-wave kernel holds
  * every live channel resident; 0 = by channel count only).  Bits are the
- * same either way.  Values above 32,768 are for diagnostics only: the
+ * same either way.  An engine of at most 32,768 channels is also governed
+ * by it when it is set below the engine's channel count: superframes with
+ * more live channels than live_max then run one lane per channel.  Values
+ * above 32,768 are for diagnostics only: the
  * four-wave kernel then loops over the extra live channels and is slower
  * than the lane kernel from about 40,960 live (profiles/r05_mw_crossover.jsonl). */
 int melpe_engine_set_mw_live_max(melpe_engine *e, int live_max);
@@ -498,14 +501,93 @@ const char *melpe_last_error(void);
  *   locked, 0x10 frequency locked, low nibble symbol errors).  Optional
  *   out C x calls x 12 gets data after every call, ret C x calls int32 the
  *   return values.  A call needs 1080 samples from pos (rx.c:246); one that
- *   would read past stride returns -1 and ends that channel's launch. */
+ *   would read past stride returns -1 and ends that channel's launch.
+ *   A caller who wants packets and speech rather than status rows uses
+ *   melpe_rx_line_dev below, which reads the status on the device. */
 int melpe_modem_state_bytes(void);
 int melpe_modem_reset_dev(void *d_state, int channels, const void *d_mask, void *hip_stream);
+/* the same fresh records written into host memory (no GPU), for callers who
+ * keep the state on the host (melpe_rx_line_host) or upload it themselves */
+int melpe_modem_reset_host(void *state, int channels);
 int melpe_modulate_dev(void *d_state, const void *d_pkts, void *d_pcm, int channels, int packets,
 		       const void *d_active, void *hip_stream);
 int melpe_demodulate_dev(void *d_state, const void *d_pcm, long stride, void *d_pos, void *d_data,
 			 void *d_out, void *d_ret, int channels, int calls, const void *d_active,
 			 void *hip_stream);
+
+/* The receive loop, line samples to speech in one call: the RX mirror of
+ * melpe_tx_dev.  Per active channel of the engine it is rx.c:294-378 with the
+ * playback buffer always empty, `calls` times:
+ *   1. Demodulate at d_pos[c], which advances by the return value -- exactly
+ *      melpe_demodulate_dev's call (d_pcm, stride, d_pos and d_data are its
+ *      arguments; a call that would read past stride ends the channel's work
+ *      for this launch).
+ *   2. If the call flagged a block ready (buf[11] & 0x80): when the block lag
+ *      is locked (& 0x40), fber *= 0.99, fber += buf[11] & 0x0F; buf[11] =
+ *      0xFE; when locked, ProcessPkt on buf IN PLACE -- at step >= 5 the
+ *      ProcessCtr of melpe_link_rx_dev on the channel's link record; a value
+ *      >= 0 is a control packet (fau *= 0.99, fau += value), -3 is voice
+ *      (buf[11] = 0xFF); below step 5 the value is MELPE_LINK_STAGE with
+ *      record and packet untouched, and the block counts as silence.  The
+ *      block goes into the channel's next output slot, then buf[11] = 0.
+ *   3. After the calls, slot j of the channel is melpe_s of its 11 bytes if
+ *      voice, else 540 zero samples (rx.c:356-360), on the engine's decoder
+ *      state through the engine's own decode launch (lane order, both decoder
+ *      mappings).
+ * d_data is the buffer the next Demodulate call receives and now carries
+ * ProcessPkt's changes as rx.c's buf does.  That would show only in a block
+ * the demodulator forces out at a frame's end without rewriting the buffer
+ * (status 0xCF), which would be processed as the previous block's ProcessPkt
+ * left it.  From a reset modem record that path cannot be reached (within a
+ * 15-call frame the bit position always meets the lag once, so a block is
+ * always handed out before the frame's end); the reference never took it on
+ * any test line, and it is covered by construction -- one buffer, as in
+ * rx.c -- not by a test.
+ *
+ * d_rx_state: C records of melpe_rx_line_state_bytes() = 16 bytes (device,
+ * 4-byte aligned), the loop's own statics; zeroed = a fresh process:
+ *     0  float  fber    averaged symbol errors per block (rx.c:150)
+ *     4  float  fau     averaged authentication level (rx.c:151)
+ *     8  uint32 blocks  ready blocks seen
+ *    12  reserved, zero
+ * d_modem_state and d_link_state are melpe_demodulate_dev's and
+ * melpe_link_rx_dev's records; finv stays the caller's business.
+ *
+ * Outputs are slot-major (slot j is a contiguous C-row block):
+ *   d_bits  slots x C x 11      the block's bytes after ProcessPkt
+ *   d_voice slots x C bytes     1 = voice
+ *   d_sp    slots x C x 540 int16 (8-byte aligned)  decoded PCM or zeros
+ *   d_info  slots x C x 8 bytes (4-byte aligned), per block:
+ *             byte 0     index of the call that produced it (mod 256)
+ *             byte 1     buf[11] as Demodulate left it
+ *             byte 2     kind: 0 lag not locked, 1 control, 2 voice,
+ *                        3 MELPE_LINK_STAGE
+ *             byte 3     zero
+ *             bytes 4..7 int32 ProcessPkt's value, MELPE_LINK_STAGE, or
+ *                        MELPE_RX_NOLOCK for kind 0
+ *   d_count C bytes             the channel's ready blocks of this launch
+ * Slots at and past d_count[c] are not written in any buffer; an inactive
+ * channel (d_active[c] == 0) keeps its records, every row and its d_count.
+ * One block is ready per 15-call modem frame, so slots >= calls / 15 + 2 (and
+ * <= 255) is required; whatever its input, the kernel writes no slot >= slots.
+ * An engine call like melpe_rx_stream_dev: ordered on hip_stream, serialised
+ * with the engine's other calls, no allocation, no host synchronisation; one
+ * loop kernel, one zero fill and `slots` decode launches.
+ * melpe_rx_line_host takes host buffers (outputs go up too, so unwritten rows
+ * keep the caller's bytes) and runs the same launches.
+ * melpe_rx_line_private_bytes: the loop kernel's private segment per lane
+ * (diagnostics; the engine reserves its scratch at create). */
+#define MELPE_RX_NOLOCK (-102)
+int melpe_rx_line_state_bytes(void);
+int melpe_rx_line_private_bytes(void);
+int melpe_rx_line_dev(melpe_engine *e, void *d_modem_state, void *d_link_state, void *d_rx_state,
+		      const void *d_pcm, long stride, void *d_pos, void *d_data, void *d_sp,
+		      void *d_bits, void *d_voice, void *d_info, void *d_count, int calls, int slots,
+		      const void *d_active, void *hip_stream);
+int melpe_rx_line_host(melpe_engine *e, void *modem_state, void *link_state, void *rx_state,
+		       const int16_t *pcm, long stride, int32_t *pos, uint8_t *data, int16_t *sp,
+		       unsigned char *bits, uint8_t *voice, uint8_t *info, uint8_t *count, int calls,
+		       int slots, const uint8_t *active);
 
 /* Device basic-op self-test: out[i] = op(a[i], b[i], c[i]) evaluated by the
  * device build of the saturating basic operators, op ids of

@@ -10,5 +10,6 @@ from .codec import (MelpeEngine, Melpe, load_library, LIB_PATH,  # noqa: F401
 from .codec import VoiceEnc, VoiceDec, Vad, stream_pack, stream_unpack  # noqa: F401
 from .codec import stream_pack_dev, stream_pack_work_bytes  # noqa: F401
 from .codec import Link, LINK_RECORD, LINK_REKEY, LINK_STAGE  # noqa: F401
+from .codec import RxLine, RX_LINE_RECORD, RX_LINE_INFO, RX_NOLOCK, rx_line_slots  # noqa: F401
 from .codec import PAR_WORDS, QPAR_WORDS  # noqa: F401
 from . import params  # noqa: F401

@@ -145,7 +145,7 @@ def device_disassembly(obj, arch=None):
 # to the private segment is aperture-checked before its offset is added,
 # which faulted on gfx950 (kern.h FLAT_GUARD_BYTES)
 NO_FLAT = ("k_enc_ana", "k_enc_quant", "k_enc_harm", "k_enc_tail", "k_decode", "k_vad", "k_enc_npp", "k_npp",
-           "k_demodulate", "k_enc24",
+           "k_demodulate", "k_rx_line", "k_enc24",
            "k_dec24", "k_helpers_eval", "k_stream", "k_dsp_eval", "k_parse", "k_par_tap")
 
 

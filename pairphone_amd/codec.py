@@ -51,6 +51,7 @@ def load_library(path=None):
         "melpe_engine_import": (i32, [vp, i32, i32, i32, vp]),
         "melpe_modem_state_bytes": (i32, []),
         "melpe_modem_reset_dev": (i32, [vp, i32, vp, vp]),
+        "melpe_modem_reset_host": (i32, [vp, i32]),
         "melpe_modulate_dev": (i32, [vp, vp, vp, i32, i32, vp, vp]),
         "melpe_demodulate_dev": (i32, [vp, vp, ctypes.c_long, vp, vp, vp, vp, i32, i32, vp, vp]),
         "melpe_ops_eval_dev": (i32, [i32, vp, vp, vp, vp, ctypes.c_long, vp]),
@@ -104,6 +105,12 @@ def load_library(path=None):
         "melpe_stream_pack_work_bytes": (ctypes.c_long, [i32]),
         "melpe_stream_pack_dev": (i32, [vp, vp, vp, vp, vp, vp, i32, vp, vp]),
         "melpe_rx_stream_dev": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "melpe_rx_line_state_bytes": (i32, []),
+        "melpe_rx_line_private_bytes": (i32, []),
+        "melpe_rx_line_dev": (i32, [vp, vp, vp, vp, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                    vp, vp]),
+        "melpe_rx_line_host": (i32, [vp, vp, vp, vp, vp, ctypes.c_long, vp, vp, vp, vp, vp, vp, vp, i32, i32,
+                                     vp]),
         "melpe_encode2400_dev": (i32, [vp, vp, vp, vp, vp]),
         "melpe_decode2400_dev": (i32, [vp, vp, vp, vp, vp]),
         "melpe_encode2400_host": (i32, [vp, vp, vp, vp]),
@@ -309,6 +316,52 @@ class Link:
     def rx_dev(self, d_state, d_pkts, d_ret, d_voice=None, packets=1, d_active=None, stream=None):
         _check(self.lib.melpe_link_rx_dev(d_state, d_pkts, d_ret, d_voice, self.C, int(packets), d_active,
                                           stream))
+
+
+RX_NOLOCK = -102     # MELPE_RX_NOLOCK: a block whose lag was not locked, ProcessPkt not run
+RX_KIND_NOLOCK, RX_KIND_CONTROL, RX_KIND_VOICE, RX_KIND_STAGE = 0, 1, 2, 3
+
+# one channel's record of the receive loop, and one block's info row (include/melpe_batch.h)
+RX_LINE_RECORD = np.dtype([("fber", "<f4"), ("fau", "<f4"), ("blocks", "<u4"), ("rsv", "<u4")])
+RX_LINE_INFO = np.dtype([("call", "u1"), ("status", "u1"), ("kind", "u1"), ("zero", "u1"), ("ret", "<i4")])
+
+
+def rx_line_slots(calls):
+    """the fewest output slots melpe_rx_line_dev accepts for `calls` calls"""
+    return int(calls) // 15 + 2
+
+
+class RxLine:
+    """The three per-channel state arrays of the receive loop
+    (MelpeEngine.rx_line / rx_line_dev) for C channels: `modem` (C x
+    melpe_modem_state_bytes, a fresh process's values), `link` (C x 256, a
+    Link's records: write them as Link.setup does, or assign Link.state) and
+    `rx` (C x 16: fber, fau, blocks seen; zero = fresh), plus the cursors
+    `pos` (C int32) and the demodulator's persistent buf `data` (C x 12)."""
+
+    def __init__(self, channels):
+        self.lib = load_library()
+        self.C = int(channels)
+        if self.lib.melpe_rx_line_state_bytes() != RX_LINE_RECORD.itemsize:
+            raise RuntimeError("libmelpe_amd: receive-loop record of %d bytes"
+                               % self.lib.melpe_rx_line_state_bytes())
+        self.modem = np.zeros((self.C, self.lib.melpe_modem_state_bytes()), np.uint8)
+        _check(self.lib.melpe_modem_reset_host(_ptr(self.modem), self.C))
+        self.link = np.zeros((self.C, self.lib.melpe_link_state_bytes()), np.uint8)
+        self.rx = np.zeros((self.C, RX_LINE_RECORD.itemsize), np.uint8)
+        self.pos = np.zeros(self.C, np.int32)
+        self.data = np.zeros((self.C, 12), np.uint8)
+
+    def fields(self):
+        """the receive-loop records as a structured array (a copy): fber, fau, blocks"""
+        return self.rx.reshape(-1).view(RX_LINE_RECORD).copy()
+
+    def set_fields(self, rec):
+        self.rx[:] = np.ascontiguousarray(rec, RX_LINE_RECORD).view(np.uint8).reshape(self.C, -1)
+        return self
+
+    def link_fields(self):
+        return self.link.reshape(-1).view(LINK_RECORD).copy()
 
 
 class Vad:
@@ -568,6 +621,39 @@ class MelpeEngine:
         d_pos_next (None, or d_pos itself) receives the advanced cursors"""
         _check(self.lib.melpe_rx_stream_dev(self.h, d_stream, d_pos, d_end, d_pos_next, d_sp,
                                             d_bits, d_voiced, d_lens, d_active, stream))
+
+    def rx_line_dev(self, d_modem_state, d_link_state, d_rx_state, d_pcm, stride, d_pos, d_data, d_sp,
+                    d_bits, d_voice, d_info, d_count, calls=15, slots=None, d_active=None, stream=None):
+        """the receive loop on device pointers (melpe_rx_line_dev): `calls`
+        Demodulate calls per channel on d_pcm (C x stride int16) from d_pos,
+        every ready block through ProcessPkt in place and into the channel's
+        next slot, then melpe_s or 540 zeros per slot.  Outputs slot-major:
+        d_sp slots x C x 540, d_bits slots x C x 11, d_voice slots x C,
+        d_info slots x C x 8, d_count C."""
+        slots = rx_line_slots(calls) if slots is None else int(slots)
+        _check(self.lib.melpe_rx_line_dev(self.h, d_modem_state, d_link_state, d_rx_state, d_pcm, int(stride),
+                                          d_pos, d_data, d_sp, d_bits, d_voice, d_info, d_count, int(calls),
+                                          slots, d_active, stream))
+
+    def rx_line(self, state, pcm, calls=15, slots=None, active=None, fill=0):
+        """the receive loop on host buffers (melpe_rx_line_host): `state` an
+        RxLine (updated in place, cursors included), pcm C x stride int16.
+        Returns (sp slots x C x 540, bits slots x C x 11, voice slots x C,
+        info slots x C as RX_LINE_INFO, count C); rows at and past count[c],
+        and those of inactive channels, hold `fill`."""
+        C = self.channels
+        pcm = np.ascontiguousarray(pcm, np.int16).reshape(C, -1)
+        slots = rx_line_slots(calls) if slots is None else int(slots)
+        sp = np.full((slots, C, SF_SAMPLES), fill, np.int16)
+        bits = np.full((slots, C, SF_BYTES), fill, np.uint8)
+        voice = np.full((slots, C), fill, np.uint8)
+        info = np.full((slots, C, RX_LINE_INFO.itemsize), fill, np.uint8)
+        count = np.full(C, fill, np.uint8)
+        act = None if active is None else np.ascontiguousarray(active, np.uint8).reshape(C)
+        _check(self.lib.melpe_rx_line_host(self.h, _ptr(state.modem), _ptr(state.link), _ptr(state.rx), _ptr(pcm),
+                                           pcm.shape[1], _ptr(state.pos), _ptr(state.data), _ptr(sp), _ptr(bits),
+                                           _ptr(voice), _ptr(info), _ptr(count), int(calls), slots, _ptr(act)))
+        return sp, bits, voice, info.reshape(-1).view(RX_LINE_INFO).reshape(slots, C), count
 
     def decode_streams(self, streams):
         """melpe_dec for C files at once: `streams` is one VAD-framed byte

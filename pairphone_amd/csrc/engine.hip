@@ -38,6 +38,7 @@
 #include "dsp_eval_modes.h"
 #define MODEM_FN __host__ __device__ static inline
 #include "modem.h"
+#include "rxline.h"
 #include "../../include/melpe.h"
 #include "../../include/melpe_batch.h"
 
@@ -419,22 +420,14 @@ __device__ __forceinline__ int demod_stage(int16_t *w, const int16_t *src, int n
 	return sh;
 }
 
-__global__ __launch_bounds__(WAVE) void k_demodulate(ModemState *st, const int16_t *pcm, long stride,
-						     int32_t *pos, uint8_t *data, uint8_t *out,
-						     int32_t *ret, int channels, int calls,
-						     const uint8_t *active)
+/* `calls` successive calls of one lane on its staged window, from sample
+ * offset p of its row x; after(k, r) runs after call k with its return value
+ * (-1: the call would have read past the row, and the lane stops).  Returns
+ * the offset after the last call. */
+template <class F>
+__device__ __forceinline__ int32_t demod_calls(DemodLane &L, const int16_t *x, long stride, int32_t p,
+						uint8_t *d, int calls, F &&after)
 {
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= channels || (active && !active[c]))
-		return;
-	DemodLane L;
-	PIN_FRAME(L);
-	L.S = st[c];
-	uint8_t d[12];
-	for (int i = 0; i < 12; i++)
-		d[i] = data[12L * c + i];
-	int32_t p = pos[c];
-	const int16_t *x = pcm + (long) c * stride;
 	int32_t r = 0;
 	for (int k0 = 0; k0 < calls && r >= 0; k0 += DEMOD_CALLS) {
 		const int nk = calls - k0 < DEMOD_CALLS ? calls - k0 : DEMOD_CALLS;
@@ -453,19 +446,143 @@ __global__ __launch_bounds__(WAVE) void k_demodulate(ModemState *st, const int16
 				r = modem_demod(&L.S, L.w + (p - base), d);
 				p += r;
 			}
-			if (out)
-				for (int i = 0; i < 12; i++)
-					out[((long) c * calls + k) * 12 + i] = d[i];
-			if (ret)
-				ret[(long) c * calls + k] = r;
+			after(k, r);
 			if (r < 0)
 				break;
 		}
 	}
+	return p;
+}
+
+__global__ __launch_bounds__(WAVE) void k_demodulate(ModemState *st, const int16_t *pcm, long stride,
+						     int32_t *pos, uint8_t *data, uint8_t *out,
+						     int32_t *ret, int channels, int calls,
+						     const uint8_t *active)
+{
+	int c = blockIdx.x * WAVE + threadIdx.x;
+	if (c >= channels || (active && !active[c]))
+		return;
+	DemodLane L;
+	PIN_FRAME(L);
+	L.S = st[c];
+	uint8_t d[12];
+	for (int i = 0; i < 12; i++)
+		d[i] = data[12L * c + i];
+	const int32_t p = demod_calls(L, pcm + (long) c * stride, stride, pos[c], d, calls, [&](int k, int32_t r) {
+		if (out)
+			for (int i = 0; i < 12; i++)
+				out[((long) c * calls + k) * 12 + i] = d[i];
+		if (ret)
+			ret[(long) c * calls + k] = r;
+	});
 	st[c] = L.S;
 	pos[c] = p;
 	for (int i = 0; i < 12; i++)
 		data[12L * c + i] = d[i];
+}
+
+/*
+ * The receive loop (rx.c:294-361, rxline.h): k_demodulate's lane and window,
+ * with the ready-block step run inside the call loop on the lane's buf --
+ * the fber update, ProcessCtr on the channel's link record (loaded at the
+ * event and stored after it: its 32 soft bits would otherwise sit in the
+ * lane's registers through every Demodulate call), the fau update -- and the
+ * block handed out into the channel's next slot.  Lanes of a wave reach their
+ * events at different calls, so the wave may run the branch in every
+ * iteration; no lane waits on another, and every loop is bounded by `calls`
+ * or a constant.
+ *
+ * Outputs are slot-major (slot j = rows j * channels ...).  A lane writes the
+ * bytes of its own rows only: an 11-byte bits row as the bytes up to its
+ * first dword boundary, whole dwords, and the bytes after the last; the
+ * 8-byte info row as two dwords; nothing at or past `slots`.
+ */
+typedef uint32_t rxl_u32a __attribute__((__may_alias__));
+
+__device__ __forceinline__ void rxl_store_bits(uint8_t *row, const uint8_t *d)
+{
+	const int head = (int) ((4 - ((uintptr_t) row & 3)) & 3);
+	int i = 0;
+	for (; i < head; i++)
+		row[i] = d[i];
+	for (; i + 4 <= VC_PKT_BYTES; i += 4)
+		*(rxl_u32a *) (row + i) = (uint32_t) d[i] | ((uint32_t) d[i + 1] << 8) |
+					  ((uint32_t) d[i + 2] << 16) | ((uint32_t) d[i + 3] << 24);
+	for (; i < VC_PKT_BYTES; i++)
+		row[i] = d[i];
+}
+
+__global__ __launch_bounds__(WAVE) void k_rx_line(ModemState *st, LinkState *lk, RxLineState *rx,
+						  const int16_t *pcm, long stride, int32_t *pos, uint8_t *data,
+						  uint8_t *bits, uint8_t *voice, uint32_t *info, uint8_t *count,
+						  int channels, int calls, int slots, const uint8_t *active)
+{
+	int c = blockIdx.x * WAVE + threadIdx.x;
+	if (c >= channels || (active && !active[c]))
+		return;
+	DemodLane L;
+	PIN_FRAME(L);
+	L.S = st[c];
+	uint8_t d[12];
+	for (int i = 0; i < 12; i++)
+		d[i] = data[12L * c + i];
+	float fber = rx[c].fber, fau = rx[c].fau;
+	uint32_t blocks = rx[c].blocks;
+	int n = 0;	/* blocks handed out by this launch */
+	const int32_t p = demod_calls(L, pcm + (long) c * stride, stride, pos[c], d, calls, [&](int k, int32_t r) {
+		if (r < 0 || !(d[11] & 0x80))
+			return;
+		const RxLineEvent ev = rxline_block(d, &lk[c], &fber, &fau);
+		blocks++;
+		if (n < slots) {
+			const long row = (long) n * channels + c;
+			rxl_store_bits(bits + row * VC_PKT_BYTES, d);
+			voice[row] = ev.kind == RXL_KIND_VOICE;
+			uint32_t w0, w1;
+			rxline_info(&ev, k, &w0, &w1);
+			info[2 * row] = w0;
+			info[2 * row + 1] = w1;
+			n++;
+		}
+		d[11] = 0;	/* rx.c:361: the block is taken, the output slot being free */
+	});
+	st[c] = L.S;
+	pos[c] = p;
+	for (int i = 0; i < 12; i++)
+		data[12L * c + i] = d[i];
+	rx[c].fber = fber;
+	rx[c].fau = fau;
+	rx[c].blocks = blocks;
+	count[c] = (uint8_t) n;
+}
+
+/* after k_rx_line: 540 zero samples for every slot that holds a block which
+ * is not voice (rx.c:360), one wave per (slot, channel) */
+__global__ __launch_bounds__(STREAM_BLOCK) void k_rx_line_zero(uint2 *sp, const uint8_t *voice,
+								 const uint8_t *count, const uint8_t *active,
+								 int channels, int slots)
+{
+	const int words = (int) (MELPE_SF_SAMPLES * sizeof(int16_t) / sizeof(uint2));
+	const long w = blockIdx.x * (long) (STREAM_BLOCK / WAVE) + threadIdx.x / WAVE;
+	if (w >= (long) slots * channels)
+		return;
+	const int j = (int) (w / channels), c = (int) (w - (long) j * channels);
+	if ((active && !active[c]) || j >= count[c] || voice[w])
+		return;
+	uint2 *row = sp + w * words;
+	for (int i = threadIdx.x & (WAVE - 1); i < words; i += WAVE)
+		row[i] = make_uint2(0u, 0u);
+}
+
+/* the decoder's mask of slot j: the channels whose block j is voice */
+__global__ __launch_bounds__(STREAM_BLOCK) void k_rx_line_mask(uint8_t *mask, const uint8_t *voice,
+								 const uint8_t *count, const uint8_t *active,
+								 int channels, int j)
+{
+	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
+	if (c >= channels)
+		return;
+	mask[c] = (!active || active[c]) && j < count[c] && voice[(long) j * channels + c];
 }
 
 __global__ __launch_bounds__(WAVE) void k_modem_reset(ModemState *st, const uint8_t *mask, int channels)
@@ -828,6 +945,7 @@ struct melpe_engine {
 	int16_t *d_pcm = nullptr;	/* staging for *_host calls */
 	unsigned char *d_bits = nullptr;
 	uint8_t *d_mask = nullptr;
+	uint8_t *d_rxmask = nullptr;	/* melpe_rx_line_dev: the decoder's mask of the slot in hand */
 	int16_t *d_npp = nullptr;	/* staging of melpe_npp_host, grown on demand */
 	BinBuf bin_enc, bin_dec;	/* pitch-class lane order of k_enc_ana / k_decode */
 	BinBuf bin_enc2;	/* voicing-pattern lane order of k_enc_quant / k_enc_harm / k_enc_tail */
@@ -1459,7 +1577,11 @@ static int engine_reserve(melpe_engine *e)
 			lane = kl_quant_private();
 		/* (k_parse's frame, the record's excitation side, is far below
 		 * the decoder's: it never sets the maximum and needs no warm-up) */
-		const size_t dec_lane = kl_dec_private() > kl_parse_private() ? kl_dec_private() : kl_parse_private();
+		size_t dec_lane = kl_dec_private() > kl_parse_private() ? kl_dec_private() : kl_parse_private();
+		/* (nor does the receive loop's, the demodulator's window plus a
+		 * link record: melpe_rx_line_private_bytes) */
+		if ((size_t) melpe_rx_line_private_bytes() > dec_lane)
+			dec_lane = (size_t) melpe_rx_line_private_bytes();
 		const size_t per_wave = (lane > dec_lane ? lane : dec_lane) * WAVE;
 		const size_t mw_wave = kl_ana_mw_private() * WAVE;
 		const size_t ww = kl_npp_private() > kl_harm_wave_private() ? kl_npp_private() : kl_harm_wave_private();
@@ -1525,6 +1647,7 @@ int melpe_engine_create(melpe_engine **out, int device, int channels)
 	CREATE_STEP(hipMalloc(&e->d_pcm, sizeof(int16_t) * MELPE_SF_SAMPLES * (size_t) channels));
 	CREATE_STEP(hipMalloc(&e->d_bits, (size_t) MELPE_SF_BYTES * channels));
 	CREATE_STEP(hipMalloc(&e->d_mask, (size_t) channels));
+	CREATE_STEP(hipMalloc(&e->d_rxmask, (size_t) channels));
 	CREATE_STEP(bin_alloc(&e->bin_enc, channels));
 	CREATE_STEP(bin_alloc(&e->bin_dec, channels));
 	CREATE_STEP(bin_alloc(&e->bin_enc2, channels));
@@ -1637,6 +1760,7 @@ int melpe_engine_destroy(melpe_engine *e)
 	hipFree(e->d_pcm);
 	hipFree(e->d_bits);
 	hipFree(e->d_mask);
+	hipFree(e->d_rxmask);
 	hipFree(e->bin_enc.perm);
 	hipFree(e->bin_dec.perm);
 	hipFree(e->bin_enc2.perm);
@@ -2373,6 +2497,16 @@ int melpe_modem_reset_dev(void *d_state, int channels, const void *d_mask, void 
 	return 0;
 }
 
+/* the same records written on the host (no GPU): what a caller uploads */
+int melpe_modem_reset_host(void *state, int channels)
+{
+	if (!state || channels <= 0 || ((uintptr_t) state & 3))
+		return fail_msg("melpe_modem_reset_host: bad arguments");
+	for (int c = 0; c < channels; c++)
+		modem_reset((ModemState *) state + c);
+	return 0;
+}
+
 int melpe_modulate_dev(void *d_state, const void *d_pkts, void *d_pcm, int channels, int packets,
 		       const void *d_active, void *hip_stream)
 {
@@ -2836,6 +2970,106 @@ int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos
 		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
 					       (const uint8_t *) d_voiced, s));
 		return 0;
+	});
+}
+
+/* the receive loop (k_rx_line, rxline.h) */
+int melpe_rx_line_state_bytes(void)
+{
+	return (int) sizeof(RxLineState);
+}
+
+int melpe_rx_line_private_bytes(void)
+{
+	return (int) private_bytes((const void *) k_rx_line);
+}
+
+/* argument errors, refused before any HIP call */
+static int rx_line_args(const char *who, const melpe_engine *e, const void *modem, const void *link,
+			const void *rx, const void *pcm, long stride, const void *pos, const void *data,
+			const void *sp, const void *bits, const void *voice, const void *info,
+			const void *count, int calls, int slots, bool dev)
+{
+	const std::string w(who);
+	if (calls <= 0 || stride < MODEM_LOOKAHEAD)
+		return fail_msg(w + ": calls must be positive and stride at least one call's 1,080 samples");
+	if (slots < calls / 15 + 2 || slots > 255)
+		return fail_msg(w + ": slots must be at least calls / 15 + 2 (and at most 255)");
+	if (!modem || !link || !rx)
+		return fail_msg(w + ": null state pointer");
+	if (!pcm || !pos || !data || !sp || !bits || !voice || !info || !count)
+		return fail_msg(w + ": null buffer pointer");
+	if (((uintptr_t) modem & 3) || ((uintptr_t) link & 3) || ((uintptr_t) rx & 3))
+		return fail_msg(w + ": state records must be 4-byte aligned");
+	if (dev && (((uintptr_t) sp & 7) || ((uintptr_t) pos & 3) || ((uintptr_t) info & 3) || ((uintptr_t) pcm & 1)))
+		return fail_msg(w + ": sp must be 8-byte, pos and info 4-byte aligned");
+	if (!e)
+		return fail_msg(w + ": null engine");
+	return 0;
+}
+
+int melpe_rx_line_dev(melpe_engine *e, void *d_modem_state, void *d_link_state, void *d_rx_state,
+		      const void *d_pcm, long stride, void *d_pos, void *d_data, void *d_sp, void *d_bits,
+		      void *d_voice, void *d_info, void *d_count, int calls, int slots, const void *d_active,
+		      void *hip_stream)
+{
+	if (int rc = rx_line_args("melpe_rx_line_dev", e, d_modem_state, d_link_state, d_rx_state, d_pcm, stride,
+				  d_pos, d_data, d_sp, d_bits, d_voice, d_info, d_count, calls, slots, true))
+		return rc;
+	const int n = e->channels;
+	const uint8_t *act = (const uint8_t *) d_active, *voice = (const uint8_t *) d_voice;
+	const uint8_t *count = (const uint8_t *) d_count;
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		k_rx_line<<<grid_for(n), WAVE, 0, s>>>(
+			(ModemState *) d_modem_state, (LinkState *) d_link_state, (RxLineState *) d_rx_state,
+			(const int16_t *) d_pcm, stride, (int32_t *) d_pos, (uint8_t *) d_data, (uint8_t *) d_bits,
+			(uint8_t *) d_voice, (uint32_t *) d_info, (uint8_t *) d_count, n, calls, slots, act);
+		HIPCHK(hipGetLastError());
+		const long rows = (long) slots * n, per = STREAM_BLOCK / WAVE;
+		k_rx_line_zero<<<(unsigned) ((rows + per - 1) / per), STREAM_BLOCK, 0, s>>>(
+			(uint2 *) d_sp, voice, count, act, n, slots);
+		HIPCHK(hipGetLastError());
+		/* slot by slot, as the channel's decoder state carries from block to block */
+		for (int j = 0; j < slots; j++) {
+			k_rx_line_mask<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
+				e->d_rxmask, voice, count, act, n, j);
+			HIPCHK(hipGetLastError());
+			HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp + (size_t) j * n * MELPE_SF_SAMPLES,
+						       (const uint8_t *) d_bits + (size_t) j * n * MELPE_SF_BYTES,
+						       e->d_rxmask, s));
+		}
+		return 0;
+	});
+}
+
+/* host buffers: one staged upload per tensor (outputs too, so that rows the
+ * call does not write keep the caller's bytes), the same launches, and back */
+int melpe_rx_line_host(melpe_engine *e, void *modem_state, void *link_state, void *rx_state, const int16_t *pcm,
+		       long stride, int32_t *pos, uint8_t *data, int16_t *sp, unsigned char *bits, uint8_t *voice,
+		       uint8_t *info, uint8_t *count, int calls, int slots, const uint8_t *active)
+{
+	if (int rc = rx_line_args("melpe_rx_line_host", e, modem_state, link_state, rx_state, pcm, stride, pos, data,
+				  sp, bits, voice, info, count, calls, slots, false))
+		return rc;
+	DEVGUARD(e->device);
+	const size_t n = (size_t) e->channels, rows = n * (size_t) slots;
+	/* sp first: the stage buffer's start is its only 8-byte aligned part */
+	Xfer x[] = {{sp, nullptr, rows * MELPE_SF_SAMPLES * sizeof(int16_t), XFER_IN | XFER_OUT},
+		    {modem_state, nullptr, n * sizeof(ModemState), XFER_IN | XFER_OUT},
+		    {link_state, nullptr, n * LINK_STATE_BYTES, XFER_IN | XFER_OUT},
+		    {rx_state, nullptr, n * sizeof(RxLineState), XFER_IN | XFER_OUT},
+		    {pos, nullptr, n * sizeof(int32_t), XFER_IN | XFER_OUT},
+		    {info, nullptr, rows * RXL_INFO_BYTES, XFER_IN | XFER_OUT},
+		    {pcm, nullptr, n * (size_t) stride * sizeof(int16_t), XFER_IN},
+		    {data, nullptr, n * 12, XFER_IN | XFER_OUT},
+		    {bits, nullptr, rows * MELPE_SF_BYTES, XFER_IN | XFER_OUT},
+		    {voice, nullptr, rows, XFER_IN | XFER_OUT},
+		    {count, nullptr, n, XFER_IN | XFER_OUT},
+		    {active, nullptr, n, XFER_IN}};
+	return stage_host_call("melpe_rx_line_host", x, 12, [&] {
+		return melpe_rx_line_dev(e, x[1].dev, x[2].dev, x[3].dev, x[6].dev, stride, x[4].dev, x[7].dev,
+					 x[0].dev, x[8].dev, x[9].dev, x[5].dev, x[10].dev, calls, slots, x[11].dev,
+					 nullptr);
 	});
 }
 

@@ -24,6 +24,7 @@
 #include "link.h"
 #include "vad.h"
 #include "modem.h"
+#include "rxline.h"
 
 using namespace mlp;
 
@@ -644,6 +645,64 @@ int emu_demodulate(unsigned char *state, const int16_t *pcm, long stride, int32_
 			ret[(size_t) c * calls + k] = r;
 			if (r < 0)
 				break;
+		}
+	}
+	return 0;
+}
+
+/* host build of the receive loop (rxline.h), same layout as
+ * melpe_rx_line_host: per active channel `calls` Demodulate calls with the
+ * ready-block step between them, then slot by slot melpe_s or 540 zeros on
+ * the engine's decoder records */
+int emu_rx_line_state_bytes(void)
+{
+	return (int) sizeof(RxLineState);
+}
+
+int emu_rx_line(emu_engine *e, unsigned char *modem_state, unsigned char *link_state, unsigned char *rx_state,
+		const int16_t *pcm, long stride, int32_t *pos, uint8_t *data, int16_t *sp, unsigned char *bits,
+		uint8_t *voice, uint8_t *info, uint8_t *count, int calls, int slots, const uint8_t *active)
+{
+	const int C = e->channels;
+	if (slots < calls / 15 + 2 || slots > 255)
+		return -1;
+	for (int c = 0; c < C; c++) {
+		if (active && !active[c])
+			continue;
+		ModemState *S = (ModemState *) modem_state + c;
+		LinkState *lk = (LinkState *) link_state + c;
+		RxLineState *rx = (RxLineState *) rx_state + c;
+		uint8_t *d = data + 12 * (size_t) c;
+		int n = 0;
+		for (int k = 0; k < calls; k++) {
+			if (pos[c] < 0 || pos[c] + MODEM_LOOKAHEAD > stride)
+				break;
+			pos[c] += modem_demod(S, pcm + (size_t) c * stride + pos[c], d);
+			if (!(d[11] & 0x80))
+				continue;
+			const RxLineEvent ev = rxline_block(d, lk, &rx->fber, &rx->fau);
+			rx->blocks++;
+			if (n < slots) {
+				const size_t row = (size_t) n * C + c;
+				uint32_t w[2];
+				memcpy(bits + row * VC_PKT_BYTES, d, VC_PKT_BYTES);
+				voice[row] = ev.kind == RXL_KIND_VOICE;
+				rxline_info(&ev, k, &w[0], &w[1]);
+				memcpy(info + row * RXL_INFO_BYTES, w, RXL_INFO_BYTES);
+				n++;
+			}
+			d[11] = 0;
+		}
+		count[c] = (uint8_t) n;
+		for (int j = 0; j < n; j++) {
+			const size_t row = (size_t) j * C + c;
+			int16_t *out = sp + row * BLOCK;
+			if (voice[row]) {
+				memcpy(e->dec[c].chbuf, bits + row * VC_PKT_BYTES, VC_PKT_BYTES);
+				decode_superframe(&e->dec[c], out);
+			} else {
+				memset(out, 0, sizeof(int16_t) * BLOCK);
+			}
 		}
 	}
 	return 0;
