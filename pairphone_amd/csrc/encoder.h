@@ -526,8 +526,19 @@ MN void analysis_tail(EncAna *E)
 			true, 7);
 	quant_bp(E, par);
 	quant_jitter(E, par);
-	for (int i = 0; i < NF; i++)
+	/* the unvoiced frames' 8192s and frame last's magnitudes (quant.h
+	 * fsmag_last), as k_enc_harm; the census build counts the reference's
+	 * find_harm on every voiced frame */
+#if !defined(MELPE_OPCOUNT)
+	const int last = fsmag_last(par);
+#endif
+	for (int i = 0; i < NF; i++) {
+#if !defined(MELPE_OPCOUNT)
+		if (!par[i].uv_flag && i != last)
+			continue;
+#endif
 		ana_fsmag_frame(E, &par[i], i);
+	}
 	ana_pack(E);
 }
 
@@ -535,12 +546,12 @@ MN void analysis_tail(EncAna *E)
  * k_enc_ana, k_quant.hip k_enc_quant, k_harm.hip):
  * analysis_a1 runs the three frames and sc_ana, after which the caller does
  * the history shift (ana_shift);
- * analysis_q runs the quantisers and writes each voiced frame's windowed
- * residual of the quantised LSFs to res[i * LPC_FRAME ..]
- * (melp_ana.c:224-233, the input of find_harm; an unvoiced frame's row is
- * not written);
- * the magnitudes go into par[i].fs_mag (k_enc_harm), then analysis_b packs
- * the superframe.
+ * analysis_q runs the quantisers and writes the last voiced frame's windowed
+ * residual of the quantised LSFs to res[last * LPC_FRAME ..]
+ * (melp_ana.c:224-233, the input of find_harm; no other row is written:
+ * quant.h fsmag_last);
+ * its magnitudes go into par[last].fs_mag (k_enc_harm), then analysis_b
+ * packs the superframe.
  * The cut after sc_ana is where the superframe's voicing pattern becomes
  * known: everything from lsf_vq on branches on it, so the engine sorts the
  * lanes by it between the two kernels.  Of hpspeech analysis_q reads only
@@ -589,17 +600,15 @@ MN void analysis_q(EncAna *E, int16_t *res)
 			true, 7);
 	quant_bp(E, par);
 	quant_jitter(E, par);
-	for (int i = 0; i < NF; i++) {
-		if (par[i].uv_flag)
-			continue;
-		int16_t lpc[LPC_ORD + 1];
-		lpc[0] = 4096;
-		lpc_lsp2pred(par[i].lsf, &lpc[1], LPC_ORD);
-		zerflt(&E->hpspeech[i * FRAME + FRAME_END - LPC_FRAME / 2], lpc, E->sigbuf, LPC_ORD,
-		       LPC_FRAME);
-		window(E->sigbuf, TB(win_cof), E->sigbuf, LPC_FRAME);
-		v_copy(&res[i * LPC_FRAME], E->sigbuf, LPC_FRAME);
-	}
+	const int i = fsmag_last(par);
+	if (i < 0)
+		return;
+	int16_t lpc[LPC_ORD + 1];
+	lpc[0] = 4096;
+	lpc_lsp2pred(par[i].lsf, &lpc[1], LPC_ORD);
+	zerflt(&E->hpspeech[i * FRAME + FRAME_END - LPC_FRAME / 2], lpc, E->sigbuf, LPC_ORD, LPC_FRAME);
+	window(E->sigbuf, TB(win_cof), E->sigbuf, LPC_FRAME);
+	v_copy(&res[i * LPC_FRAME], E->sigbuf, LPC_FRAME);
 }
 
 /* the history shift at the end of analysis (melp_ana.c:262) */

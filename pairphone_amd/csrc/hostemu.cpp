@@ -151,18 +151,21 @@ int emu_encode_ana_split(emu_engine *e, unsigned char *bits, const int16_t *sp)
 		memcpy((char *) E + o2, (const char *) R + o2, n2);
 		memcpy(&E->hpspeech[ANA_RES_BEG], res, sizeof(int16_t) * (ANA_RES_END - ANA_RES_BEG));
 		for (int k = 0; k < NF * LPC_FRAME; k++)
-			res[k] = (int16_t) 0x5a5a;	/* unvoiced rows stay unread */
+			res[k] = (int16_t) 0x5a5a;	/* every row but frame last's stays unread */
 		analysis_q(E, res);
 		memcpy((char *) R + o, (const char *) E + o, n);
 		memcpy((char *) R + o2, (const char *) E + o2, n2);
-		/* k_enc_harm and k_enc_tail, on the record */
+		/* k_enc_harm and k_enc_tail, on the record: the unvoiced frames'
+		 * 8192s and frame last's magnitudes; the other voiced frames' stay
+		 * as the record holds them */
 		E = R;
-		for (int i = 0; i < NF; i++) {
-			MelpParam *par = &E->par[i];
-			v_set(par->fs_mag, 8192, NUM_HARM);
-			if (!par->uv_flag)
-				find_harm(&res[i * LPC_FRAME], par->fs_mag, par->pitch, NUM_HARM, LPC_FRAME);
-		}
+		for (int i = 0; i < NF; i++)
+			if (E->par[i].uv_flag)
+				v_set(E->par[i].fs_mag, 8192, NUM_HARM);
+		const int last = fsmag_last(E->par);
+		if (last >= 0)
+			find_harm(&res[last * LPC_FRAME], E->par[last].fs_mag, E->par[last].pitch, NUM_HARM,
+				  LPC_FRAME);
 		analysis_b(E);
 		for (int k = 0; k < 11; k++)
 			bits[c * 11 + k] = E->chbuf[k];
@@ -178,6 +181,43 @@ int emu_encode_ana(emu_engine *e, unsigned char *bits, const int16_t *sp)
 			bits[c * 11 + k] = e->enc[c].a.chbuf[k];
 	}
 	return 0;
+}
+
+/* the analysis in the reference's literal order, every voiced frame's
+ * Fourier magnitudes computed, cut after `upto` stages (encoder.h
+ * analysis_upto, what k_enc_ana_dbg runs): the independent form the product
+ * forms above are compared with */
+int emu_encode_ana_upto(emu_engine *e, unsigned char *bits, const int16_t *sp, int upto)
+{
+	for (int c = 0; c < e->channels; c++) {
+		analysis_upto(&e->enc[c].a, sp + (size_t) c * BLOCK, upto);
+		for (int k = 0; k < 11; k++)
+			bits[c * 11 + k] = e->enc[c].a.chbuf[k];
+	}
+	return 0;
+}
+
+/* where the tests find fields in an exported encoder record (EncState), in
+ * bytes: the analysis state, its live prefix's length, par[0], par's stride,
+ * uv_flag within a par, fsm_prev_uv and chbuf within the analysis state;
+ * returns how many there are */
+int emu_enc_layout(long *out, int n)
+{
+	const long v[] = {(long) offsetof(EncState, a),       (long) ENC_ANA_LIVE,
+			  (long) offsetof(EncAna, par),       (long) sizeof(MelpParam),
+			  (long) offsetof(MelpParam, uv_flag), (long) offsetof(EncAna, fsm_prev_uv),
+			  (long) offsetof(EncAna, chbuf)};
+	const int m = (int) (sizeof v / sizeof v[0]);
+	for (int i = 0; i < n && i < m; i++)
+		out[i] = v[i];
+	return m;
+}
+
+/* the live prefix of channel c's analysis state (ENC_ANA_LIVE bytes) */
+long emu_enc_live(emu_engine *e, int c, unsigned char *out)
+{
+	memcpy(out, &e->enc[c].a, ENC_ANA_LIVE);
+	return (long) ENC_ANA_LIVE;
 }
 
 #if !defined(MELPE_OPCOUNT)

@@ -5,8 +5,9 @@
  *
  * In the lane-per-channel analysis each lane ran find_harm's 512-point real
  * FFT alone, 2 KB of private state per channel: 12% of k_enc_ana at
- * 262,144 channels.  Here k_enc_quant (k_quant.hip) leaves each voiced
- * frame's windowed residual (analysis_q), k_enc_harm runs the FFT across the 64
+ * 262,144 channels.  Here k_enc_quant (k_quant.hip) leaves the windowed
+ * residual of the last voiced frame, the only one whose magnitudes are read
+ * (analysis_q, quant.h fsmag_last), k_enc_harm runs the FFT across the 64
  * lanes of a wave in LDS -- the NPP's wave FFT (npp_wave.h wv_cfft256: the
  * same fft_lib.c cfft, same per-stage guard scaling) plus rfft's split and
  * twiddle passes with one step per lane -- and the harmonic peak search, and
@@ -138,9 +139,11 @@ MD void wv_find_harm(const int16_t v[4], int16_t *fsmag, Word16 pitch, uint32_t 
 	wsync();
 }
 
-/* the windowed residuals k_enc_quant left in res;
+/* the windowed residual k_enc_quant left in res;
  * one wave per live channel: slot g runs channel perm[g] (the engine's
- * lane order) or channel g under the mask; the three frames in order */
+ * lane order) or channel g under the mask; the three frames in order, of
+ * which only frame last runs the FFT (the loop is the form the goldens
+ * hold for: DESIGN.md section 2) */
 __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t *res,
 						   const uint8_t *active, int n, const int *perm,
 						   const int *nlive, AnaGate gate)
@@ -155,6 +158,15 @@ __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t 
 		return;
 	}
 	const int lane = threadIdx.x;
+	/* the one frame whose magnitudes quant_fsmag reads (quant.h fsmag_last);
+	 * an all-unvoiced channel leaves ahead of the twiddle and window loads */
+	const int last = fsmag_last(enc[c].a.par);
+	if (last < 0) {
+		if (lane < NUM_HARM)
+			for (int i = 0; i < NF; i++)
+				enc[c].a.par[i].fs_mag[lane] = 8192;
+		return;
+	}
 	__shared__ uint32_t x[512];
 	WvConst kc;
 	wv_const_init(&kc, lane);
@@ -166,6 +178,8 @@ __global__ __launch_bounds__(WAVE) void k_enc_harm(EncState *enc, const int16_t 
 				par->fs_mag[lane] = 8192;
 			continue;
 		}
+		if (i != last)	/* quant_fsmag overwrites it */
+			continue;
 		int16_t v[4];
 		const int16_t *w = res + ((size_t) c * NF + i) * LPC_FRAME;
 #pragma unroll

@@ -1,8 +1,8 @@
 /*
  * k_quant.hip -- the quantisers of melpe_a between sc_ana and the Fourier
  * magnitudes (melpe/melp_ana.c:164-233: lsf_vq, pitch_vq, gain_vq, the
- * jitter and bandpass quantisers, and each voiced frame's windowed residual
- * of the quantised LSFs), one lane per channel.
+ * jitter and bandpass quantisers, and the last voiced frame's windowed
+ * residual of the quantised LSFs), one lane per channel.
  *
  * lsf_vq branches on the superframe's voicing pattern, and a wave pays the
  * union of its lanes' branches: every codebook scan runs once per distinct
@@ -30,10 +30,10 @@ struct QuantLane {
 };
 
 /* res: the channel's row of NF x LPC_FRAME samples.  In: the pre-shift
- * speech span k_enc_ana exported at its start (ANA_XSPAN_*).  Out: each
- * voiced frame's windowed residual at i * LPC_FRAME, for k_enc_harm.  The
- * rows overlap the span, so the span is taken into the lane's frame whole
- * before analysis_q writes any row. */
+ * speech span k_enc_ana exported at its start (ANA_XSPAN_*).  Out: the
+ * last voiced frame's windowed residual at last * LPC_FRAME, for k_enc_harm.
+ * The rows overlap the span, so the span is taken into the lane's frame
+ * whole before analysis_q writes its row. */
 __global__ __launch_bounds__(WAVE, MELPE_QUANT_WAVES) void k_enc_quant(EncState *enc, int16_t *res,
 									const uint8_t *active, int n,
 									const int *perm, const int *nlive,

@@ -1025,20 +1025,44 @@ MN void quant_jitter(EncAna *E, MelpParam *par)
 	E->qpar.jit_index[0] = flag;
 }
 
-/* quant_fsmag :1277 */
+/* The one frame of the superframe whose computed Fourier magnitudes anything
+ * reads: the last voiced one, or -1 when all are unvoiced.  quant_fsmag
+ * (qnt12.c:1277-1356) vector-quantises par[last].fs_mag alone and overwrites
+ * every other voiced frame's with qmag, prev_fsmag or a mix of the two, in
+ * each of its branches (:1303-1349); prev_fsmag then is par[NF-1]'s, which
+ * when voiced is frame last's.  So the residual, its window, the FFT
+ * (melp_ana.c:223-236) and window_Q of the other voiced frames reach no bit
+ * and no state, and the encoder runs them for frame last only.  Valid once
+ * the voicing is final, after quant_bp and quant_jitter, where the
+ * reference tests uv_flag for find_harm. */
+MD int fsmag_last(const MelpParam *par)
+{
+	int last = -1;
+	for (int i = 0; i < NF; i++)
+		if (!par[i].uv_flag)
+			last = i;
+	return last;
+}
+
+/* quant_fsmag :1277; the other voiced frames' fs_mag come in as anything
+ * (fsmag_last) except in the census build, which counts the reference's
+ * window_Q on each */
 MN void quant_fsmag(EncAna *E, MelpParam *par)
 {
 	PROF_SCOPE(13);
 	int16_t qmag[NUM_HARM];
-	int cnt = 0, last = -1;
+	int cnt = 0;
+	const int last = fsmag_last(par);
 	for (int i = 0; i < NF; i++) {
 		if (par[i].uv_flag) {
 			v_set(par[i].fs_mag, 8192, NUM_HARM);
-		} else {
-			window_Q(par[i].fs_mag, g_der.w_fs, par[i].fs_mag, NUM_HARM, 14);
-			last = i;
-			cnt++;
+			continue;
 		}
+#if !defined(MELPE_OPCOUNT)
+		if (i == last)
+#endif
+			window_Q(par[i].fs_mag, g_der.w_fs, par[i].fs_mag, NUM_HARM, 14);
+		cnt++;
 	}
 	if (cnt > 0)
 		vq_enc<NUM_HARM>(TB(fsvq_cb), par[last].fs_mag, 256, qmag, &E->qpar.fs_index);
