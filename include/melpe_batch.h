@@ -640,6 +640,16 @@ int melpe_dsp_scalar_dev(int mode, int lds_tables, const void *d_args, void *d_o
 			 void *hip_stream);
 int melpe_dsp_wave_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
 		       void *hip_stream);
+/* Device self-test of the encoder's pitch and voicing analysis, function by
+ * function or call sequence by call sequence (pairphone_amd/csrc/ana_eval.h;
+ * modes and case layout in ana_eval_modes.h): n lanes, lane i on its AE_IN
+ * int16 of d_in with the AE_ARGS int32 of d_args, AE_OUT int32 per lane in
+ * d_out.  melpe_ana_scalar_dev: the pitch tracker's scalars, out[i] =
+ * f(args[4i .. 4i+3]), int32.  tests/test_device_ana.py compares each with
+ * the reference's own functions. */
+int melpe_ana_eval_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream);
+int melpe_ana_scalar_dev(int mode, const void *d_args, void *d_out, long n, void *hip_stream);
 
 /* Diagnostics: per-stage wave-cycle totals of a profiling build
  * (libmelpe_amd_prof.so, -DMELPE_PROF; tools/stage_prof.py,

@@ -60,6 +60,8 @@ def load_library(path=None):
         "melpe_encode_host_wait": (i32, [vp]),
         "melpe_helpers_eval_dev": (i32, [i32, vp, vp, vp, i32, vp]),
         "melpe_dsp_eval_dev": (i32, [i32, vp, vp, vp, i32, vp]),
+        "melpe_ana_eval_dev": (i32, [i32, vp, vp, vp, i32, vp]),
+        "melpe_ana_scalar_dev": (i32, [i32, vp, vp, ctypes.c_long, vp]),
         "melpe_dsp_scalar_dev": (i32, [i32, i32, vp, vp, ctypes.c_long, vp]),
         "melpe_dsp_wave_dev": (i32, [i32, vp, vp, vp, i32, vp]),
         "melpe_encode_host": (i32, [vp, vp, vp, vp]),

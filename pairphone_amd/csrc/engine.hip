@@ -36,6 +36,7 @@
 #include "ops_eval.h"
 #include "helpers_eval.h"
 #include "dsp_eval_modes.h"
+#include "ana_eval_modes.h"
 #define MODEM_FN __host__ __device__ static inline
 #include "modem.h"
 #include "rxline.h"
@@ -2602,6 +2603,34 @@ int melpe_dsp_eval_dev(int mode, const void *d_in, const void *d_args, void *d_o
 	if (int rc = kl_dsp_eval(mode, (const int16_t *) d_in, (const int32_t *) d_args, (int32_t *) d_out, n,
 				 (hipStream_t) hip_stream))
 		return fail("melpe_dsp_eval_dev", (hipError_t) rc);
+	return 0;
+}
+
+int melpe_ana_eval_dev(int mode, const void *d_in, const void *d_args, void *d_out, int n,
+		       void *hip_stream)
+{
+	if (!d_in || !d_args || !d_out || n < 0 || mode < 0 || mode >= AE_MODE_COUNT)
+		return fail_msg("melpe_ana_eval_dev: bad arguments");
+	if (n == 0)
+		return 0;
+	if (int rc = current_device_tables())
+		return rc;
+	if (int rc = kl_ana_eval(mode, (const int16_t *) d_in, (const int32_t *) d_args, (int32_t *) d_out, n,
+				 (hipStream_t) hip_stream))
+		return fail("melpe_ana_eval_dev", (hipError_t) rc);
+	return 0;
+}
+
+int melpe_ana_scalar_dev(int mode, const void *d_args, void *d_out, long n, void *hip_stream)
+{
+	if (!d_args || !d_out || n < 0 || n > 0x7fffffffL || mode < 0 || mode >= AE_SCALAR_COUNT)
+		return fail_msg("melpe_ana_scalar_dev: bad arguments");
+	if (n == 0)
+		return 0;
+	if (int rc = current_device_tables())
+		return rc;
+	if (int rc = kl_ana_scalar(mode, (const int32_t *) d_args, (int32_t *) d_out, n, (hipStream_t) hip_stream))
+		return fail("melpe_ana_scalar_dev", (hipError_t) rc);
 	return 0;
 }
 

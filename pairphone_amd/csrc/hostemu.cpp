@@ -19,6 +19,7 @@
 #endif
 #include "helpers_eval.h"
 #include "dsp_eval.h"
+#include "ana_eval.h"
 #include "codec2400.h"
 #include "voice_crypt.h"
 #include "link.h"
@@ -305,6 +306,36 @@ int emu_dsp_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out,
 		for (int k = 0; k < DE_IN; k++)
 			o[DE_RET + k] = b[k];
 	}
+	return 0;
+}
+
+/* host build of the analysis parity test (ana_eval.h), same layouts as
+ * melpe_ana_eval_dev */
+int emu_ana_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n)
+{
+	if (mode < 0 || mode >= AE_MODE_COUNT)
+		return -1;
+	for (int i = 0; i < n; i++) {
+		alignas(4) int16_t b[AE_WIN] = {0};
+		int32_t r[AE_RET] = {0};
+		EncAna E;
+		memset(&E, 0, sizeof E);
+		ae_eval(mode, in + (size_t) i * AE_IN, b, &E, args + (size_t) i * AE_ARGS, r);
+		int32_t *o = out + (size_t) i * AE_OUT;
+		for (int k = 0; k < AE_RET; k++)
+			o[k] = r[k];
+		for (int k = 0; k < AE_WIN; k++)
+			o[AE_RET + k] = b[k];
+	}
+	return 0;
+}
+
+int emu_ana_scalar(int mode, const int32_t *args, int32_t *out, long n)
+{
+	if (mode < 0 || mode >= AE_SCALAR_COUNT)
+		return -1;
+	for (long i = 0; i < n; i++)
+		out[i] = ae_scalar(mode, args[4 * i], args[4 * i + 1], args[4 * i + 2], args[4 * i + 3]);
 	return 0;
 }
 

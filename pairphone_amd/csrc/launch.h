@@ -26,7 +26,7 @@ struct LinkState;
 /* the translation units that carry their own copy of the constant tables:
  * MELPE_TU(name) in the TU's .hip is the one definition site, this list the
  * one place that names them all (tests/test_abi.py holds the two equal) */
-#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(quant) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(par)
+#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(quant) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(anaeval) X(par)
 
 extern "C" {
 
@@ -83,6 +83,11 @@ int kl_dec24(mlp::DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t
  * blob-table scalar modes; the wave forms are next to the code they test */
 int kl_dsp_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
 int kl_dsp_scalar(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
+
+/* k_ana_eval.hip: the function-level parity test of the pitch and voicing
+ * analysis (ana_eval.h) */
+int kl_ana_eval(int mode, const int16_t *in, const int32_t *args, int32_t *out, int n, hipStream_t s);
+int kl_ana_scalar(int mode, const int32_t *args, int32_t *out, long n, hipStream_t s);
 
 /* k_par.hip: the parameter tap (rec + c * stride + off is channel c's
  * par[0]) and the parse-only decoder, rows as dwords */

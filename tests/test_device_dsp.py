@@ -83,9 +83,10 @@ def ref_run(kind, mode, inp, args):
     return out if kind == "s" else out.reshape(n, -1)
 
 
-def first_diff(what, got, want, describe=None):
+def first_diff(what, got, want, describe=None, where=None):
     """exact equality; the message names the mode, the case and the first
-    differing output"""
+    differing output (where(j): what output j of a case is, e.g. the call of
+    a sequence it belongs to)"""
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, "%s: shape %s, reference %s" % (what, got.shape, want.shape)
     if np.array_equal(got, want):
@@ -93,9 +94,11 @@ def first_diff(what, got, want, describe=None):
     bad = np.argwhere(got != want)
     idx = tuple(int(v) for v in bad[0])
     extra = " [%s]" % describe(idx[0]) if describe else ""
+    out = idx[1:] if len(idx) > 1 else ""
+    if where and len(idx) == 2:
+        out = "%d (%s)" % (idx[1], where(idx[1]))
     pytest.fail("%s: %d outputs differ in %d cases; first: case %d%s output %s = %d, reference %d" % (
-        what, len(bad), len(np.unique(bad[:, 0])), idx[0], extra,
-        idx[1:] if len(idx) > 1 else "", got[idx], want[idx]))
+        what, len(bad), len(np.unique(bad[:, 0])), idx[0], extra, out, got[idx], want[idx]))
 
 
 # ------------------------------------------------------------- scalar cases
