@@ -245,6 +245,61 @@ int melpe_decode_params_host(melpe_engine *e, int16_t *par, const uint8_t *activ
 int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits,
 		     const uint8_t *active);
 
+/* Speech from parameter rows: the other direction of the tensors above.
+ *
+ * Per active channel the call is the reference's synthesis() (melpe/
+ * melp_syn.c:110-146) at 1200 bps with its build switch SKIP_CHANNEL
+ * (melpe/sc1200.h:53) on -- the analysis-to-synthesis loop without a channel:
+ * the samples carried from the last superframe are laid down, no erasure is
+ * in force, and melp_syn runs on the three rows.  It runs on the channel's
+ * decoder state.  par (C x 3 x 30 int16, device rows 4-byte aligned) is read
+ * only and never modified; sp is C x 540 int16 as for melpe_decode.
+ *
+ * PRE-HEAD ROWS.  par holds melp_par as a channel reader or the analysis
+ * leaves it, BEFORE the parameter head of melp_syn (the noise estimate and
+ * suppression on the gains, the unvoiced fill, the un-weighting of fs_mag,
+ * the LSF bandwidth clamp): the call runs that head itself.  The rows of
+ * melpe_encode_params are such rows.  The rows of melpe_parse and
+ * melpe_decode_params are POST-head (melp_par as melp_syn left it); feeding
+ * them back applies the head twice -- the gains are suppressed again and the
+ * magnitudes un-weighted again -- which is no error the call can detect.
+ *
+ * Row admission.  Each frame's row is clamped, on the lane's private copy
+ * and before anything else reads it, to what the synthesis needs to stay
+ * inside its tables and bounded loops (the same function on the device and in
+ * the host build, decoder.h syn_row_admit; the ranges are in DESIGN.md §2):
+ *   uv_flag  any nonzero value becomes 1
+ *   pitch    [0, 32767]   (voiced frames; an unvoiced frame's pitch, jitter
+ *   jitter   [0, 8192]     and fs_mag are overwritten by the head and are
+ *   fs_mag   [0, 32767]    not looked at)
+ *   lsf      [0, 32767]   (any order: the head sorts and spaces them)
+ *   gain     [0, 20480]   (0 .. 80 dB)
+ *   bpvc     [0, 16384]
+ * Every row a channel reader (erased superframes included) or the analysis
+ * can emit passes unchanged; after admission the synthesis is total for any
+ * int16 row.  status (C bytes, optional; NULL = not wanted): 0 when the
+ * channel's three rows were used as given, 1 when any field was clamped.  The
+ * reference defines the output only for rows with status 0.
+ *
+ * Afterwards melpe_decode_params returns melp_par as melp_syn left it
+ * (post-head), as after a decode.  The channel reader's history is not
+ * touched, so a channel is synthesised from rows, parsed, or decoded from its
+ * reset (melpe_engine_reset, which = 2), not a mixture.  Inactive channels
+ * keep state, PCM and status.  An engine call like melpe_decode_dev: ordered
+ * on hip_stream, serialised with the engine's other calls, no allocation, no
+ * host synchronisation; melpe_engine_set_lane_order and
+ * melpe_engine_set_dec_waves govern it as they govern the decode (its lane
+ * order is cut by the rows of the superframe being synthesised).
+ *
+ * melpe_synth_params_private_bytes: the kernels' private segment per lane
+ * (waves = 1 lane form, 2 two-wave form; diagnostics, the engine reserves its
+ * scratch at create). */
+int melpe_synth_params_dev(melpe_engine *e, void *d_sp, const void *d_par, void *d_status,
+			   const void *d_active, void *hip_stream);
+int melpe_synth_params_host(melpe_engine *e, int16_t *sp, const int16_t *par, uint8_t *status,
+			    const uint8_t *active);
+int melpe_synth_params_private_bytes(int waves);
+
 /* The 2400 bps MELP mode (54 bits per 180-sample frame, in 7 bytes), which
  * the reference compiles but cannot reach through melpe_i (melpe/melpe.c:76
  * pins RATE1200): per active channel, encode2400 = npp of the frame at

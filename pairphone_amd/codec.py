@@ -78,6 +78,9 @@ def load_library(path=None):
         "melpe_encode_params_host": (i32, [vp, vp, vp, vp]),
         "melpe_decode_params_host": (i32, [vp, vp, vp]),
         "melpe_parse_host": (i32, [vp, vp, vp, vp]),
+        "melpe_synth_params_dev": (i32, [vp, vp, vp, vp, vp, vp]),
+        "melpe_synth_params_host": (i32, [vp, vp, vp, vp, vp]),
+        "melpe_synth_params_private_bytes": (i32, [i32]),
         "melpe_npp_host": (i32, [vp, vp, i32, i32, vp]),
         "melpe_npp_dev": (i32, [vp, vp, i32, i32, vp, vp]),
         "melpe_synth_seed": (i32, [vp, u32, u32]),
@@ -548,6 +551,30 @@ class MelpeEngine:
 
     def parse_dev(self, d_par, d_bits, d_active=None, stream=None):
         _check(self.lib.melpe_parse_dev(self.h, d_par, d_bits, d_active, stream))
+
+    def synth_params(self, par, active=None, sp=None, status=None):
+        """Speech from parameter rows: the synthesis without a channel, on the
+        channels' decoder state.  par: int16 [C, 3, 30] as the channel reader
+        or the analysis leaves melp_par (the rows of encode_params; NOT those
+        of parse / decode_params, on which the synthesis' parameter head has
+        already run); never written.  Returns int16 [C, 540]; `status`
+        (uint8 [C], optional) receives 1 where a field had to be clamped into
+        the admitted range, else 0.  Inactive channels keep what `sp` /
+        `status` hold.  A channel is synthesised from rows, parsed or decoded
+        from its reset, not a mixture."""
+        par = np.ascontiguousarray(par, dtype=np.int16)
+        assert par.shape == (self.channels, 3, PAR_WORDS)
+        if sp is None:
+            sp = np.zeros((self.channels, SF_SAMPLES), dtype=np.int16)
+        assert sp.dtype == np.int16 and sp.shape == (self.channels, SF_SAMPLES) and sp.flags.c_contiguous
+        if status is not None:
+            assert status.dtype == np.uint8 and status.shape == (self.channels,) and status.flags.c_contiguous
+        _check(self.lib.melpe_synth_params_host(self.h, _ptr(sp), _ptr(par), _ptr(status),
+                                                _ptr(self._mask(active))))
+        return sp
+
+    def synth_params_dev(self, d_sp, d_par, d_status=None, d_active=None, stream=None):
+        _check(self.lib.melpe_synth_params_dev(self.h, d_sp, d_par, d_status, d_active, stream))
 
     def encode2400(self, sp, active=None):
         """2400 bps mode: one 180-sample frame per channel. sp: int16 [C, 180],

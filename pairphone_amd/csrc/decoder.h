@@ -1665,6 +1665,84 @@ MN void melp_syn(DecState *D, MelpParam *par, int16_t *out)
 	syn_frame_end(D, par, F);
 }
 
+/* ------------------------------------------------------------------ */
+/* synthesis from parameter rows (k_syn.hip): synthesis() of            */
+/* melp_syn.c:110-146 with the reference's SKIP_CHANNEL on              */
+/* ------------------------------------------------------------------ */
+
+#ifndef MELPE_HD
+#if defined(__HIPCC__)
+#define MELPE_HD __host__ __device__
+#else
+#define MELPE_HD
+#endif
+#endif
+
+/* the admitted range of each field of a caller's row (DESIGN.md §2 has the
+ * derivation): each is the domain the reference's arithmetic was written for,
+ * not the narrower set a quantiser emits */
+#define ADM_GAIN_MAX_Q8 20480	/* 80 dB, MAX_NOISE_Q8: above it scale_adj's exponent wraps in extract_l */
+#define ADM_BPVC_MAX_Q14 16384
+
+MELPE_HD inline bool syn_admit_field(int16_t *v, int lo, int hi)
+{
+	const int x = *v, y = x < lo ? lo : (x > hi ? hi : x);
+	*v = (int16_t) y;
+	return y != x;
+}
+
+/* Row admission: clamps one frame's row, field by field, to what melp_syn's
+ * call tree needs to stay inside its tables and bounded loops, and returns
+ * whether anything changed.  Runs on the lane's private copy before anything
+ * else reads the row.  The one clamp memory safety rests on is the pitch's
+ * sign: syn_period takes sqrt_fxp of the interpolated pitch, whose log10_fxp
+ * indexes log_table with x >> 7 and has no guard below zero.  No upper or
+ * tighter lower bound is needed, and none is set: the period length is clamped
+ * to [PITCHMIN, PITCHMAX] after the jitter whatever the row holds, and the
+ * reference's own reader emits pitches a step outside [PITCHMIN_Q7,
+ * PITCHMAX_Q7] (pow10_fxp of the decoded logarithm: 2,559).  An unvoiced
+ * frame's pitch, jitter and Fourier magnitudes are not looked at: the
+ * parameter head overwrites them (syn_par_head), and the analysis leaves
+ * values of another scale there (pitch 50).  Every row a channel reader or
+ * the analysis can leave passes unchanged. */
+MELPE_HD inline bool syn_row_admit(MelpParam *p)
+{
+	bool ch = false;
+	if (p->uv_flag != 0 && p->uv_flag != 1) {	/* tested as a boolean: any nonzero is unvoiced */
+		p->uv_flag = 1;
+		ch = true;
+	}
+	if (!p->uv_flag) {
+		ch |= syn_admit_field(&p->pitch, 0, 32767);
+		ch |= syn_admit_field(&p->jitter, 0, MAX_JITTER_Q15);
+		for (int i = 0; i < NUM_HARM; i++)
+			ch |= syn_admit_field(&p->fs_mag[i], 0, 32767);
+	}
+	for (int i = 0; i < LPC_ORD; i++)
+		ch |= syn_admit_field(&p->lsf[i], 0, 32767);
+	for (int i = 0; i < NUM_GAINFR; i++)
+		ch |= syn_admit_field(&p->gain[i], 0, ADM_GAIN_MAX_Q8);
+	for (int i = 0; i < NUM_BANDS; i++)
+		ch |= syn_admit_field(&p->bpvc[i], 0, ADM_BPVC_MAX_Q14);
+	return ch;
+}
+
+/* where the decoder reads the channel: the caller's rows become melp_par
+ * (rows may be D->par itself, the kernels copy them straight there), each is
+ * admitted, and no erasure is in force (melp_syn.c:125) */
+MD void syn_rows_in(DecState *D, const MelpParam *rows, uint8_t *status)
+{
+	bool ch = false;
+	for (int i = 0; i < NF; i++) {
+		if (rows != D->par)
+			D->par[i] = rows[i];
+		ch |= syn_row_admit(&D->par[i]);
+	}
+	D->erase = 0;
+	if (status)
+		*status = ch ? 1 : 0;
+}
+
 #if !defined(MELPE_OPCOUNT)
 /* ------------------------------------------------------------------ */
 /* the two-wave decoder (k_dec2.hip): melp_syn split into the excitation */
@@ -1805,12 +1883,19 @@ MN void melp_syn_b(DecState *D, const Hb hb, int16_t *out)
  * from buffer (p - 1) & 1 into out (B also lays down the previous
  * superframe's carried samples at p = 0).  Phases are separated by a
  * barrier; the buffers are the only data the two waves share. */
-template <class Hb>
-MD void dec2_phase(DecState *D, int16_t *out, Hb hb0, Hb hb1, int role, int p)
+template <class Hb, bool ROWS = false>
+MD void dec2_phase(DecState *D, int16_t *out, Hb hb0, Hb hb1, int role, int p, const MelpParam *rows = nullptr,
+		   uint8_t *status = nullptr)
 {
 	if (role == 0) {
-		if (p == 0)
-			D->erase = low_rate_chn_read(D);
+		/* ROWS: the synthesis from parameter rows (synth_superframe), A
+		 * takes and admits them where the decoder reads the channel */
+		if (p == 0) {
+			if (ROWS)
+				syn_rows_in(D, rows, status);
+			else
+				D->erase = low_rate_chn_read(D);
+		}
 		if (p < NF)
 			melp_syn_a(D, &D->par[p], (p & 1) ? hb1 : hb0);
 	} else if (p == 0) {
@@ -1848,6 +1933,22 @@ MN void decode_superframe(DecState *D, int16_t *out)
 		if (D->syn_begin > 0 && i < NF - 1)
 			v_copy(&out[(i + 1) * FRAME], D->sigsave, D->syn_begin);
 		DEC_CKPT(i + 1);
+	}
+}
+
+/* decode_superframe with the channel read replaced by the caller's rows
+ * (syn_rows_in): synthesis() at RATE1200 with SKIP_CHANNEL.  Touches nothing
+ * of the reader's history (rd_*, qpar, chbuf).  *status (may be null): 1 when
+ * admission changed a field. */
+MN void synth_superframe(DecState *D, const MelpParam *rows, int16_t *out, uint8_t *status)
+{
+	if (D->syn_begin > 0)
+		v_copy(out, D->sigsave, D->syn_begin);
+	syn_rows_in(D, rows, status);
+	for (int i = 0; i < NF; i++) {
+		melp_syn<false>(D, &D->par[i], &out[i * FRAME]);
+		if (D->syn_begin > 0 && i < NF - 1)
+			v_copy(&out[(i + 1) * FRAME], D->sigsave, D->syn_begin);
 	}
 }
 

@@ -811,6 +811,23 @@ __device__ __forceinline__ int bin_class_uvc(const char *rec, int off_par)
 	return (par[0].uv_flag ? 4 : 0) | (par[1].uv_flag ? 2 : 0) | (par[2].uv_flag ? 1 : 0);
 }
 
+/* The lane order of the synthesis from parameter rows (synth_launch): there
+ * the superframe being synthesised is known before the launch, so the class
+ * is cut by it, not by the previous one as bin_class must for k_decode -- the
+ * voiced frames among the rows' uv_flags and the pitch the last frame will be
+ * synthesised with (an unvoiced frame runs at UV_PITCH_Q7, decoder.h
+ * syn_par_head), in 1-sample steps.  The rows are read as the caller left
+ * them, before admission: any value lands in a class. */
+#define KEY_ROWS 2	/* bin_class_rows */
+__device__ __forceinline__ int bin_class_rows(const char *row)
+{
+	const MelpParam *par = (const MelpParam *) row;
+	const int nv = (par[0].uv_flag == 0) + (par[1].uv_flag == 0) + (par[2].uv_flag == 0);
+	int b = ((par[NF - 1].uv_flag ? UV_PITCH_Q7 : par[NF - 1].pitch) >> 7) - 20;
+	b = b < 0 ? 0 : (b > BIN_PITCHES - 1 ? BIN_PITCHES - 1 : b);
+	return nv * BIN_PITCHES + b;
+}
+
 template <int KEY>
 __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t stride, int off_par,
 						   int off_uv, const uint8_t *active, int n, BinBuf b)
@@ -824,6 +841,7 @@ __global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t strid
 		int k = NOT_LIVE;
 		if (!active || active[c]) {
 			k = KEY == KEY_VOICING ? bin_class_uvc(rec + (size_t) c * stride, off_par)
+			    : KEY == KEY_ROWS  ? bin_class_rows(rec + (size_t) c * stride + off_par)
 					       : bin_class(rec + (size_t) c * stride, off_par, off_uv);
 			atomicAdd(&cnt[k], 1u);
 		}
@@ -905,6 +923,8 @@ static hipError_t bin_launch(int order, BinBuf &b, const void *rec, size_t strid
 	unsigned g = (unsigned) ((n + 255) / 256);
 	if (key == KEY_VOICING)
 		k_bin_count<KEY_VOICING><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
+	else if (key == KEY_ROWS)
+		k_bin_count<KEY_ROWS><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
 	else
 		k_bin_count<KEY_PITCH><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
 	if ((er = hipGetLastError()) != hipSuccess)
@@ -1123,6 +1143,29 @@ static int dec_launch(melpe_engine *e, int16_t *d_sp, const uint8_t *d_bits, con
 	int rc = dec_waves_for(e) == 2
 			 ? kl_decode2(e->d_dec, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_hb, s)
 			 : kl_decode(e->d_dec, d_sp, d_bits, d_act, e->channels, perm, nlive, s);
+	if (rc == 0 && on)
+		rc = (int) bin_release(b, s);
+	return rc;
+}
+
+/* The synthesis from parameter rows (k_syn.hip), mapped and ordered like the
+ * decode: the decoder's mapping choice, hand-over buffers and BinBuf, the
+ * lane order cut by the rows themselves (KEY_ROWS: the tensor is the
+ * "record", one row of 180 bytes per channel). */
+static int synth_launch(melpe_engine *e, int16_t *d_sp, const void *d_par, uint8_t *d_status,
+			const uint8_t *d_act, hipStream_t s)
+{
+	BinBuf &b = e->bin_dec;
+	bool on;
+	hipError_t er = bin_launch(e->lane_order, b, d_par, sizeof(MelpParam) * NF, 0, 0, d_act, e->channels, s, &on,
+				   KEY_ROWS);
+	if (er != hipSuccess)
+		return (int) er;
+	const int *perm = on ? b.perm : nullptr;
+	const int *nlive = on ? (const int *) (b.ctl + 2 * NBIN) : nullptr;
+	int rc = dec_waves_for(e) == 2
+			 ? kl_synth_par2(e->d_dec, d_sp, d_par, d_status, d_act, e->channels, perm, nlive, e->d_hb, s)
+			 : kl_synth_par(e->d_dec, d_sp, d_par, d_status, d_act, e->channels, perm, nlive, s);
 	if (rc == 0 && on)
 		rc = (int) bin_release(b, s);
 	return rc;
@@ -1540,7 +1583,14 @@ static int engine_warm(melpe_engine *e)
 			return fail("melpe_engine: codec kernel scratch could not be reserved", er);
 	if (e->d_hb && (er = (hipError_t) kl_dec2_warm(e->channels, e->stream)) != hipSuccess)
 		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
-
+	/* the synthesis from rows runs the decoder's call tree less the channel
+	 * read: its kernels are warmed only if a frame should come out larger */
+	if (kl_syn_private() > kl_dec_private() &&
+	    (er = (hipError_t) kl_syn_warm(e->channels, e->stream)) != hipSuccess)
+		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
+	if (e->d_hb && kl_syn2_private() > kl_dec2_private() &&
+	    (er = (hipError_t) kl_syn2_warm(e->channels, e->stream)) != hipSuccess)
+		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
 	if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
 		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
 	return 0;
@@ -1558,8 +1608,11 @@ static int engine_reserve(melpe_engine *e)
 		e->d_lq = nullptr;
 		return fail("melpe_engine_create: multi-wave score rows", er);
 	}
-	if (e->channels <= DEC2_MAX_CHANNELS &&
-	    (er = hipMalloc(&e->d_hb, sizeof(uint32_t) * kl_decode2_hb_words(e->channels))) != hipSuccess) {
+	/* (k_synth_par2 shares the buffers: the larger of the two launches' needs) */
+	size_t hbw = kl_decode2_hb_words(e->channels);
+	if (kl_synth_par2_hb_words(e->channels) > hbw)
+		hbw = kl_synth_par2_hb_words(e->channels);
+	if (e->channels <= DEC2_MAX_CHANNELS && (er = hipMalloc(&e->d_hb, sizeof(uint32_t) * hbw)) != hipSuccess) {
 		e->d_hb = nullptr;
 		return fail("melpe_engine_create: two-wave decoder hand-over buffers", er);
 	}
@@ -1583,6 +1636,11 @@ static int engine_reserve(melpe_engine *e)
 		 * link record: melpe_rx_line_private_bytes) */
 		if ((size_t) melpe_rx_line_private_bytes() > dec_lane)
 			dec_lane = (size_t) melpe_rx_line_private_bytes();
+		/* the synthesis from rows: the decoder's frame without the channel
+		 * read's (engine_warm warms it only if it is the larger) */
+		if (kl_syn_private() > dec_lane)
+			dec_lane = kl_syn_private();
+		const size_t dec2_lane = kl_dec2_private() > kl_syn2_private() ? kl_dec2_private() : kl_syn2_private();
 		const size_t per_wave = (lane > dec_lane ? lane : dec_lane) * WAVE;
 		const size_t mw_wave = kl_ana_mw_private() * WAVE;
 		const size_t ww = kl_npp_private() > kl_harm_wave_private() ? kl_npp_private() : kl_harm_wave_private();
@@ -1598,8 +1656,8 @@ static int engine_reserve(melpe_engine *e)
 		size_t need = per_wave * waves;
 		if (mw_wave * mw_waves > need)
 			need = mw_wave * mw_waves;
-		if (e->d_hb && kl_dec2_private() * WAVE * 2 * waves > need)
-			need = kl_dec2_private() * WAVE * 2 * waves;
+		if (e->d_hb && dec2_lane * WAVE * 2 * waves > need)
+			need = dec2_lane * WAVE * 2 * waves;
 		if (ww * WAVE * resident > need)
 			need = ww * WAVE * resident;
 		size_t cur = 0, mx = 0;
@@ -2159,6 +2217,51 @@ int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits, c
 	if (!e || !par || !bits)
 		return fail_msg("melpe_parse_host: null argument");
 	return params_host(e, 2, par, nullptr, bits, active);
+}
+
+/* The synthesis from parameter rows (k_syn.hip): d_par (C x 3 x 30 int16,
+ * read only) in, d_sp (C x 540) and d_status (C bytes, optional) out */
+int melpe_synth_params_dev(melpe_engine *e, void *d_sp, const void *d_par, void *d_status, const void *d_active,
+			   void *hip_stream)
+{
+	if (!e || !d_sp || !d_par)
+		return fail_msg("melpe_synth_params_dev: null argument");
+	if ((uintptr_t) d_par & 3)
+		return fail_msg("melpe_synth_params_dev: the parameter rows must be 4-byte aligned");
+	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
+		HIPCHK((hipError_t) synth_launch(e, (int16_t *) d_sp, d_par, (uint8_t *) d_status,
+						 (const uint8_t *) d_active, s));
+		return 0;
+	});
+}
+
+/* the host form stages the rows and the status bytes in the analysis'
+ * residual buffer (C x 1,200 bytes, in use only inside an encode call) */
+int melpe_synth_params_host(melpe_engine *e, int16_t *sp, const int16_t *par, uint8_t *status,
+			    const uint8_t *active)
+{
+	if (!e || !sp || !par)
+		return fail_msg("melpe_synth_params_host: null argument");
+	static_assert(PAR_ROW_BYTES + 1 <= sizeof(int16_t) * NF * LPC_FRAME && PAR_ROW_BYTES % 4 == 0,
+		      "the rows and the status bytes fit the residual buffer");
+	const size_t pb = sizeof(int16_t) * BLOCK * (size_t) e->channels, rb = PAR_ROW_BYTES * (size_t) e->channels;
+	char *d_par = (char *) e->d_res;
+	uint8_t *d_status = status ? (uint8_t *) d_par + rb : nullptr;
+	return engine_host_call(e, active,
+				{{par, d_par, rb, XFER_IN},
+				 {sp, e->d_pcm, pb, XFER_IN_MASKED | XFER_OUT},
+				 {status, d_status, (size_t) e->channels, XFER_IN_MASKED | XFER_OUT}},
+				[&](const uint8_t *m, hipStream_t s) {
+		HIPCHK((hipError_t) synth_launch(e, e->d_pcm, d_par, d_status, m, s));
+		return 0;
+	});
+}
+
+/* private-segment bytes per lane of the synthesis kernels (diagnostics):
+ * waves = 1 k_synth_par, 2 k_synth_par2 */
+int melpe_synth_params_private_bytes(int waves)
+{
+	return (int) (waves == 2 ? kl_syn2_private() : kl_syn_private());
 }
 
 /* 2400 bps mode (codec2400.h): NPP of one 180-sample frame at RATE2400

@@ -411,7 +411,80 @@ int emu_decode2(emu_engine *e, int16_t *sp, const unsigned char *bits)
 	}
 	return 0;
 }
+
+/* the two-wave synthesis from rows as k_synth_par2 runs it: emu_decode2 with
+ * wave A taking and admitting the rows (dec2_phase<Hb, true>); B's copy of
+ * par[] is a pattern, it never reads the rows */
+int emu_synth_params2(emu_engine *e, int16_t *sp, const int16_t *par, uint8_t *status)
+{
+	static uint32_t hb[2][HB_WORDS];
+	static DecState W[2];
+	for (int c = 0; c < e->channels; c++) {
+		DecState *D = &e->dec[c];
+		memset(hb, 0x5a, sizeof hb);
+		for (int r = 0; r < 2; r++)
+			W[r] = *D;
+		memcpy(W[0].par, par + (size_t) c * NF * 30, sizeof(W[0].par));
+		memset(W[1].par, 0xa5, sizeof(W[1].par));
+		uint8_t st = 0;
+		int16_t *out = sp + (size_t) c * BLOCK;
+		for (int p = 0; p < DEC2_PHASES; p++)
+			for (int r = 0; r < 2; r++)
+				dec2_phase<HostHb, true>(&W[r], out, HostHb{hb[0]}, HostHb{hb[1]}, r, p, W[r].par, &st);
+		memcpy(D, &W[0], DEC_B_BEG);
+		memcpy((char *) D + DEC_B_BEG, (const char *) &W[1] + DEC_B_BEG, sizeof(DecState) - DEC_B_BEG);
+		if (status)
+			status[c] = st;
+	}
+	return 0;
+}
 #endif
+
+/* synthesis() with SKIP_CHANNEL on every channel as k_synth_par runs it
+ * (decoder.h synth_superframe): par (C x 3 x 30, read only) in, sp (C x 540)
+ * and status (C bytes, may be null) out */
+int emu_synth_params(emu_engine *e, int16_t *sp, const int16_t *par, uint8_t *status)
+{
+	for (int c = 0; c < e->channels; c++) {
+		MelpParam rows[NF];
+		uint8_t st = 0;
+		memcpy(rows, par + (size_t) c * NF * 30, sizeof rows);
+		synth_superframe(&e->dec[c], rows, sp + (size_t) c * BLOCK, &st);
+		if (status)
+			status[c] = st;
+	}
+	return 0;
+}
+
+/* The channel reader's rows before melp_syn's parameter head: emu_parse
+ * (parse_superframe's steps, on the engine's records) with melp_par captured
+ * between low_rate_chn_read and the head.  bits (C x 11) in; par (C x 3 x 30)
+ * the pre-head rows and erase (C bytes) the reader's erasure flag out.  The
+ * engine is a reader of its own: it advances as a parse-only decoder does. */
+int emu_read_rows(emu_engine *e, int16_t *par_out, uint8_t *erase, const unsigned char *bits)
+{
+	for (int c = 0; c < e->channels; c++) {
+		DecState *D = &e->dec[c];
+		memcpy(D->chbuf, bits + (size_t) c * 11, 11);
+		D->erase = low_rate_chn_read(D);
+		memcpy(par_out + (size_t) c * NF * 30, D->par, sizeof(D->par));
+		erase[c] = (uint8_t) (D->erase != 0);
+		for (int i = 0; i < NF; i++) {
+			syn_par_head<false>(D, &D->par[i]);
+			D->prev_par = D->par[i];
+		}
+	}
+	return 0;
+}
+
+/* the admission alone (decoder.h syn_row_admit) on n frame rows in place;
+ * changed[i] = whether row i was clamped */
+int emu_row_admit(int16_t *rows, uint8_t *changed, long n)
+{
+	for (long i = 0; i < n; i++)
+		changed[i] = (uint8_t) syn_row_admit((MelpParam *) (rows + i * 30));
+	return 0;
+}
 
 /* per-superframe debug view of channel c: melp_par (3 x 30 int16) and
  * quant_par (30 int16), in the layout oracle/ref_tool.c dumps */
