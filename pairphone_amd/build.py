@@ -58,13 +58,13 @@ PROF_LIB = os.path.join(ROOT, "pairphone_amd", "libmelpe_amd_prof.so")
 
 
 TUS = ("engine", "k_npp", "k_ana", "k_quant", "k_ana_mw", "k_harm", "k_dec", "k_r24", "k_dsp_eval", "k_ana_eval",
-       "k_par", "k_link", "k_syn")
+       "k_par", "k_link")
 # the codec TUs compile their whole call tree inline, so every access to a
 # lane's private state is a scratch_/global_ instruction with counted waits
 # instead of a generic FLAT access; this is what costs compile
 # time, hence one TU per kernel, compiled in parallel
 HOT_TUS = ("k_npp", "k_ana", "k_quant", "k_ana_mw", "k_harm", "k_dec", "k_r24", "k_dsp_eval", "k_ana_eval", "k_par",
-           "k_link", "k_syn")
+           "k_link")
 # per-TU code-generation options, each kept by an A/B on MI355X: the lane
 # analysis without the scheduler's unclustered high-register-pressure
 # rescheduling stage, 25.54-25.56 -> 25.38-25.40 ms at 262,144 channels

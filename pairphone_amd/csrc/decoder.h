@@ -1666,7 +1666,7 @@ MN void melp_syn(DecState *D, MelpParam *par, int16_t *out)
 }
 
 /* ------------------------------------------------------------------ */
-/* synthesis from parameter rows (k_syn.hip): synthesis() of            */
+/* synthesis from parameter rows (k_dec.hip RowsIn): synthesis() of     */
 /* melp_syn.c:110-146 with the reference's SKIP_CHANNEL on              */
 /* ------------------------------------------------------------------ */
 
@@ -1745,7 +1745,7 @@ MD void syn_rows_in(DecState *D, const MelpParam *rows, uint8_t *status)
 
 #if !defined(MELPE_OPCOUNT)
 /* ------------------------------------------------------------------ */
-/* the two-wave decoder (k_dec2.hip): melp_syn split into the excitation */
+/* the two-wave decoder (k_dec.hip): melp_syn split into the excitation  */
 /* side (wave A) and the filter side (wave B) of the same 64 channels     */
 /* ------------------------------------------------------------------ */
 
@@ -1939,7 +1939,9 @@ MN void decode_superframe(DecState *D, int16_t *out)
 /* decode_superframe with the channel read replaced by the caller's rows
  * (syn_rows_in): synthesis() at RATE1200 with SKIP_CHANNEL.  Touches nothing
  * of the reader's history (rd_*, qpar, chbuf).  *status (may be null): 1 when
- * admission changed a field. */
+ * admission changed a field.  It holds no DEC_CKPT on purpose: k_synth_par
+ * shares k_decode's translation unit, where the checkpoint is compiled in, and
+ * runs without progress-driven priority (it never calls PP_BEGIN). */
 MN void synth_superframe(DecState *D, const MelpParam *rows, int16_t *out, uint8_t *status)
 {
 	if (D->syn_begin > 0)

@@ -10,7 +10,8 @@
  * parallel (pairphone_amd/build.py) and linked into libmelpe_amd.so:
  *   k_npp.hip  melpe_n, and the NPP half of melpe_a (melpe/melpe.c:94-96)
  *   k_ana.hip  the analysis half of melpe_a (melpe/melpe.c:97-98)
- *   k_dec.hip  melpe_s (melpe/melpe.c:102-107)
+ *   k_dec.hip  melpe_s (melpe/melpe.c:102-107), and the synthesis from
+ *              parameter rows
  * and the rest that kern.h lists; launch.h declares what this file calls in
  * them.
  * Execution model: one lane per channel (kern.h).  Per-channel
@@ -765,6 +766,16 @@ struct BinBuf {
 	bool used = false;
 };
 
+/* what a kernel is launched with: b's order and live count when the order is
+ * used, nulls (identity lanes + mask) when it is not */
+struct LaneOrder {
+	const int *perm, *nlive;
+};
+static LaneOrder bin_order(const BinBuf &b, bool on)
+{
+	return {on ? b.perm : nullptr, on ? (const int *) (b.ctl + 2 * NBIN) : nullptr};
+}
+
 static hipError_t bin_alloc(BinBuf *b, int channels)
 {
 	size_t pb = sizeof(int) * (size_t) channels, cb = sizeof(unsigned) * (2 * NBIN + 4);
@@ -811,7 +822,7 @@ __device__ __forceinline__ int bin_class_uvc(const char *rec, int off_par)
 	return (par[0].uv_flag ? 4 : 0) | (par[1].uv_flag ? 2 : 0) | (par[2].uv_flag ? 1 : 0);
 }
 
-/* The lane order of the synthesis from parameter rows (synth_launch): there
+/* The lane order of the synthesis from parameter rows (dec_launch): there
  * the superframe being synthesised is known before the launch, so the class
  * is cut by it, not by the previous one as bin_class must for k_decode -- the
  * voiced frames among the rows' uv_flags and the pitch the last frame will be
@@ -1039,8 +1050,7 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 				   d_act, e->channels, s, &on);
 	if (er != hipSuccess)
 		return (int) er;
-	const int *perm = on ? b.perm : nullptr;
-	const int *nlive = on ? (const int *) (b.ctl + 2 * NBIN) : nullptr;
+	LaneOrder o = bin_order(b, on);
 	int nw = ana_waves_for(e);
 	AnaGate all;
 	all.tag = (int *) (b.ctl + 2 * NBIN + 1);
@@ -1077,12 +1087,12 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 	}
 	int rc = 0;
 	if (dual || nw == 4)
-		rc = kl_enc_ana_mw(e->d_enc, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_lq, mw, s);
+		rc = kl_enc_ana_mw(e->d_enc, d_sp, d_bits, d_act, e->channels, o.perm, o.nlive, e->d_lq, mw, s);
 	if (rc == 0 && nw == 1) {
 		/* lane-per-channel analysis up to sc_ana (k_ana.hip), the
 		 * quantisers (k_quant.hip), the Fourier magnitudes with a wave per
 		 * channel, then the packing (k_harm.hip) */
-		rc = kl_enc_ana(e->d_enc, d_sp, d_act, e->channels, perm, nlive, e->d_res, lane, s);
+		rc = kl_enc_ana(e->d_enc, d_sp, d_act, e->channels, o.perm, o.nlive, e->d_res, lane, s);
 		/* The second lane order.  What follows sc_ana branches on the
 		 * superframe's voicing pattern (lsf_vq's codebooks and searches,
 		 * quant_fsmag, the residual loop), which the first order cannot
@@ -1098,15 +1108,14 @@ static int ana_launch(melpe_engine *e, const int16_t *d_sp, uint8_t *d_bits, con
 			rc = (int) bin_launch(1, b2, e->d_enc, sizeof(EncState),
 					      (int) (offsetof(EncState, a) + offsetof(EncAna, par)), 0, d_act,
 					      e->channels, s, &on2, KEY_VOICING, true);
-			perm = b2.perm;
-			nlive = (const int *) (b2.ctl + 2 * NBIN);
+			o = bin_order(b2, true);
 		}
 		if (rc == 0)
-			rc = kl_enc_quant(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
+			rc = kl_enc_quant(e->d_enc, e->d_res, d_act, e->channels, o.perm, o.nlive, lane, s);
 		if (rc == 0)
-			rc = kl_enc_harm(e->d_enc, e->d_res, d_act, e->channels, perm, nlive, lane, s);
+			rc = kl_enc_harm(e->d_enc, e->d_res, d_act, e->channels, o.perm, o.nlive, lane, s);
 		if (rc == 0)
-			rc = kl_enc_tail(e->d_enc, d_bits, d_act, e->channels, perm, nlive, lane, s);
+			rc = kl_enc_tail(e->d_enc, d_bits, d_act, e->channels, o.perm, o.nlive, lane, s);
 		if (rc == 0 && on)
 			rc = (int) bin_release(b2, s);
 	}
@@ -1127,48 +1136,39 @@ static int dec_waves_for(melpe_engine *e)
 	return nw == 2 && e->d_hb ? 2 : 1;
 }
 
-static int dec_launch(melpe_engine *e, int16_t *d_sp, const uint8_t *d_bits, const uint8_t *d_act,
-		      hipStream_t s)
+/* One superframe of the decoder family (k_dec.hip) from either source: the
+ * lane order in the decoder's BinBuf, the mapping choice and the hand-over
+ * buffers are the same for both.  The sort key follows the source: the
+ * channel words decode in the order of the records' previous superframe
+ * (KEY_PITCH), the parameter rows in the order of the rows themselves
+ * (KEY_ROWS: the tensor is the "record", one row of 180 bytes per channel). */
+static int dec_launch(melpe_engine *e, int16_t *d_sp, DecSrc src, const uint8_t *d_act, hipStream_t s)
 {
 	BinBuf &b = e->bin_dec;
 	bool on;
-	hipError_t er = bin_launch(e->lane_order, b, e->d_dec, sizeof(DecState),
-				   (int) offsetof(DecState, par),
-				   (int) (offsetof(DecState, qpar) + offsetof(QuantParam, uv_flag)),
-				   d_act, e->channels, s, &on);
+	hipError_t er = src.rows ? bin_launch(e->lane_order, b, src.in, sizeof(MelpParam) * NF, 0, 0, d_act,
+					      e->channels, s, &on, KEY_ROWS)
+				 : bin_launch(e->lane_order, b, e->d_dec, sizeof(DecState),
+					      (int) offsetof(DecState, par),
+					      (int) (offsetof(DecState, qpar) + offsetof(QuantParam, uv_flag)),
+					      d_act, e->channels, s, &on);
 	if (er != hipSuccess)
 		return (int) er;
-	const int *perm = on ? b.perm : nullptr;
-	const int *nlive = on ? (const int *) (b.ctl + 2 * NBIN) : nullptr;
-	int rc = dec_waves_for(e) == 2
-			 ? kl_decode2(e->d_dec, d_sp, d_bits, d_act, e->channels, perm, nlive, e->d_hb, s)
-			 : kl_decode(e->d_dec, d_sp, d_bits, d_act, e->channels, perm, nlive, s);
+	const LaneOrder o = bin_order(b, on);
+	int rc = kl_dec(dec_waves_for(e), src, e->d_dec, d_sp, d_act, e->channels, o.perm, o.nlive, e->d_hb, s);
 	if (rc == 0 && on)
 		rc = (int) bin_release(b, s);
 	return rc;
 }
 
-/* The synthesis from parameter rows (k_syn.hip), mapped and ordered like the
- * decode: the decoder's mapping choice, hand-over buffers and BinBuf, the
- * lane order cut by the rows themselves (KEY_ROWS: the tensor is the
- * "record", one row of 180 bytes per channel). */
-static int synth_launch(melpe_engine *e, int16_t *d_sp, const void *d_par, uint8_t *d_status,
-			const uint8_t *d_act, hipStream_t s)
+/* the two sources (launch.h DecSrc) */
+static DecSrc src_bits(const void *d_bits)
 {
-	BinBuf &b = e->bin_dec;
-	bool on;
-	hipError_t er = bin_launch(e->lane_order, b, d_par, sizeof(MelpParam) * NF, 0, 0, d_act, e->channels, s, &on,
-				   KEY_ROWS);
-	if (er != hipSuccess)
-		return (int) er;
-	const int *perm = on ? b.perm : nullptr;
-	const int *nlive = on ? (const int *) (b.ctl + 2 * NBIN) : nullptr;
-	int rc = dec_waves_for(e) == 2
-			 ? kl_synth_par2(e->d_dec, d_sp, d_par, d_status, d_act, e->channels, perm, nlive, e->d_hb, s)
-			 : kl_synth_par(e->d_dec, d_sp, d_par, d_status, d_act, e->channels, perm, nlive, s);
-	if (rc == 0 && on)
-		rc = (int) bin_release(b, s);
-	return rc;
+	return {0, d_bits, nullptr};
+}
+static DecSrc src_rows(const void *d_par, uint8_t *d_status)
+{
+	return {1, d_par, d_status};
 }
 
 static std::mutex g_dev_mu;
@@ -1465,9 +1465,9 @@ static int engine_streams(melpe_engine *e, bool dec)
 	if (dec) {
 		STREAM_STEP(hipEventCreateWithFlags(&ev_dec, hipEventDisableTiming));
 		STREAM_STEP(hipStreamCreateWithFlags(&cdec, hipStreamNonBlocking));
-		STREAM_STEP(kl_dec_warm(e->channels, cdec));
+		STREAM_STEP(kl_dec_warm(1, 0, e->channels, cdec));
 		if (e->d_hb)
-			STREAM_STEP(kl_dec2_warm(e->channels, cdec));
+			STREAM_STEP(kl_dec_warm(2, 0, e->channels, cdec));
 		STREAM_STEP(hipStreamSynchronize(cdec));
 	}
 #undef STREAM_STEP
@@ -1530,7 +1530,7 @@ static int pipe_step(melpe_engine *e, void *d_bits, const void *d_sp, const void
 			return rc;
 		if (dc) {
 			HIPCHK(hipStreamWaitEvent(e->cdec, e->ev_pin, 0));
-			HIPCHK((hipError_t) dec_launch(e, (int16_t *) dc->sp, (const uint8_t *) dc->bits,
+			HIPCHK((hipError_t) dec_launch(e, (int16_t *) dc->sp, src_bits(dc->bits),
 						       (const uint8_t *) dc->active, e->cdec));
 			HIPCHK(hipEventRecord(e->ev_dec, e->cdec));
 		}
@@ -1576,21 +1576,18 @@ static int engine_warm(melpe_engine *e)
 {
 	hipError_t er;
 	const int mw = e->channels < MW_MAX_CHANNELS ? e->channels : MW_MAX_CHANNELS;
-	int (*warm[])(int, hipStream_t) = {kl_npp_warm, kl_ana_warm, kl_quant_warm, kl_harm_warm, kl_ana_mw_warm,
-						    kl_dec_warm};
+	int (*warm[])(int, hipStream_t) = {kl_npp_warm, kl_ana_warm, kl_quant_warm, kl_harm_warm, kl_ana_mw_warm};
 	for (auto f : warm)
 		if ((er = (hipError_t) f(f == kl_ana_mw_warm ? mw : e->channels, e->stream)) != hipSuccess)
 			return fail("melpe_engine: codec kernel scratch could not be reserved", er);
-	if (e->d_hb && (er = (hipError_t) kl_dec2_warm(e->channels, e->stream)) != hipSuccess)
-		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
-	/* the synthesis from rows runs the decoder's call tree less the channel
-	 * read: its kernels are warmed only if a frame should come out larger */
-	if (kl_syn_private() > kl_dec_private() &&
-	    (er = (hipError_t) kl_syn_warm(e->channels, e->stream)) != hipSuccess)
-		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
-	if (e->d_hb && kl_syn2_private() > kl_dec2_private() &&
-	    (er = (hipError_t) kl_syn2_warm(e->channels, e->stream)) != hipSuccess)
-		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
+	/* the decoder family, each mapping the engine has: the channel words'
+	 * kernel always; the parameter rows' runs the same call tree less the
+	 * channel read, and is warmed only if its frame should come out larger */
+	for (int waves = 1; waves <= (e->d_hb ? 2 : 1); waves++)
+		for (int rows = 0; rows < 2; rows++)
+			if ((!rows || kl_dec_private(waves, 1) > kl_dec_private(waves, 0)) &&
+			    (er = (hipError_t) kl_dec_warm(waves, rows, e->channels, e->stream)) != hipSuccess)
+				return fail("melpe_engine: codec kernel scratch could not be reserved", er);
 	if ((er = hipStreamSynchronize(e->stream)) != hipSuccess)
 		return fail("melpe_engine: codec kernel scratch could not be reserved", er);
 	return 0;
@@ -1608,11 +1605,9 @@ static int engine_reserve(melpe_engine *e)
 		e->d_lq = nullptr;
 		return fail("melpe_engine_create: multi-wave score rows", er);
 	}
-	/* (k_synth_par2 shares the buffers: the larger of the two launches' needs) */
-	size_t hbw = kl_decode2_hb_words(e->channels);
-	if (kl_synth_par2_hb_words(e->channels) > hbw)
-		hbw = kl_synth_par2_hb_words(e->channels);
-	if (e->channels <= DEC2_MAX_CHANNELS && (er = hipMalloc(&e->d_hb, sizeof(uint32_t) * hbw)) != hipSuccess) {
+	/* (one size whichever the source: k_decode2 and k_synth_par2 share the buffers) */
+	if (e->channels <= DEC2_MAX_CHANNELS &&
+	    (er = hipMalloc(&e->d_hb, sizeof(uint32_t) * kl_dec2_hb_words(e->channels))) != hipSuccess) {
 		e->d_hb = nullptr;
 		return fail("melpe_engine_create: two-wave decoder hand-over buffers", er);
 	}
@@ -1631,16 +1626,17 @@ static int engine_reserve(melpe_engine *e)
 			lane = kl_quant_private();
 		/* (k_parse's frame, the record's excitation side, is far below
 		 * the decoder's: it never sets the maximum and needs no warm-up) */
-		size_t dec_lane = kl_dec_private() > kl_parse_private() ? kl_dec_private() : kl_parse_private();
+		size_t dec_lane = kl_dec_private(1, 0) > kl_parse_private() ? kl_dec_private(1, 0) : kl_parse_private();
 		/* (nor does the receive loop's, the demodulator's window plus a
 		 * link record: melpe_rx_line_private_bytes) */
 		if ((size_t) melpe_rx_line_private_bytes() > dec_lane)
 			dec_lane = (size_t) melpe_rx_line_private_bytes();
 		/* the synthesis from rows: the decoder's frame without the channel
 		 * read's (engine_warm warms it only if it is the larger) */
-		if (kl_syn_private() > dec_lane)
-			dec_lane = kl_syn_private();
-		const size_t dec2_lane = kl_dec2_private() > kl_syn2_private() ? kl_dec2_private() : kl_syn2_private();
+		if (kl_dec_private(1, 1) > dec_lane)
+			dec_lane = kl_dec_private(1, 1);
+		const size_t dec2_lane = kl_dec_private(2, 0) > kl_dec_private(2, 1) ? kl_dec_private(2, 0)
+										     : kl_dec_private(2, 1);
 		const size_t per_wave = (lane > dec_lane ? lane : dec_lane) * WAVE;
 		const size_t mw_wave = kl_ana_mw_private() * WAVE;
 		const size_t ww = kl_npp_private() > kl_harm_wave_private() ? kl_npp_private() : kl_harm_wave_private();
@@ -2104,8 +2100,7 @@ int melpe_decode_dev(melpe_engine *e, void *d_sp, const void *d_bits, const void
 	if (!e || !d_sp || !d_bits)
 		return fail_msg("melpe_decode_dev: null argument");
 	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
-		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
-					       (const uint8_t *) d_active, s));
+		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, src_bits(d_bits), (const uint8_t *) d_active, s));
 		return 0;
 	});
 }
@@ -2119,7 +2114,7 @@ int melpe_decode_host(melpe_engine *e, int16_t *sp, const unsigned char *bits,
 	return engine_host_call(e, active,
 				{{bits, e->d_bits, bb, XFER_IN}, {sp, e->d_pcm, pb, XFER_IN_MASKED | XFER_OUT}},
 				[&](const uint8_t *m, hipStream_t s) {
-		HIPCHK((hipError_t) dec_launch(e, e->d_pcm, e->d_bits, m, s));
+		HIPCHK((hipError_t) dec_launch(e, e->d_pcm, src_bits(e->d_bits), m, s));
 		return 0;
 	});
 }
@@ -2219,7 +2214,7 @@ int melpe_parse_host(melpe_engine *e, int16_t *par, const unsigned char *bits, c
 	return params_host(e, 2, par, nullptr, bits, active);
 }
 
-/* The synthesis from parameter rows (k_syn.hip): d_par (C x 3 x 30 int16,
+/* The synthesis from parameter rows (k_dec.hip RowsIn): d_par (C x 3 x 30 int16,
  * read only) in, d_sp (C x 540) and d_status (C bytes, optional) out */
 int melpe_synth_params_dev(melpe_engine *e, void *d_sp, const void *d_par, void *d_status, const void *d_active,
 			   void *hip_stream)
@@ -2229,8 +2224,8 @@ int melpe_synth_params_dev(melpe_engine *e, void *d_sp, const void *d_par, void 
 	if ((uintptr_t) d_par & 3)
 		return fail_msg("melpe_synth_params_dev: the parameter rows must be 4-byte aligned");
 	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
-		HIPCHK((hipError_t) synth_launch(e, (int16_t *) d_sp, d_par, (uint8_t *) d_status,
-						 (const uint8_t *) d_active, s));
+		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, src_rows(d_par, (uint8_t *) d_status),
+					       (const uint8_t *) d_active, s));
 		return 0;
 	});
 }
@@ -2252,7 +2247,7 @@ int melpe_synth_params_host(melpe_engine *e, int16_t *sp, const int16_t *par, ui
 				 {sp, e->d_pcm, pb, XFER_IN_MASKED | XFER_OUT},
 				 {status, d_status, (size_t) e->channels, XFER_IN_MASKED | XFER_OUT}},
 				[&](const uint8_t *m, hipStream_t s) {
-		HIPCHK((hipError_t) synth_launch(e, e->d_pcm, d_par, d_status, m, s));
+		HIPCHK((hipError_t) dec_launch(e, e->d_pcm, src_rows(d_par, d_status), m, s));
 		return 0;
 	});
 }
@@ -2261,7 +2256,7 @@ int melpe_synth_params_host(melpe_engine *e, int16_t *sp, const int16_t *par, ui
  * waves = 1 k_synth_par, 2 k_synth_par2 */
 int melpe_synth_params_private_bytes(int waves)
 {
-	return (int) (waves == 2 ? kl_syn2_private() : kl_syn_private());
+	return (int) kl_dec_private(waves == 2 ? 2 : 1, 1);
 }
 
 /* 2400 bps mode (codec2400.h): NPP of one 180-sample frame at RATE2400
@@ -3099,8 +3094,7 @@ int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos
 		k_stream_zero<<<(unsigned) (((long) n + STREAM_BLOCK / WAVE - 1) / (STREAM_BLOCK / WAVE)),
 				STREAM_BLOCK, 0, s>>>((uint2 *) d_sp, (const uint8_t *) d_lens, n);
 		HIPCHK(hipGetLastError());
-		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, (const uint8_t *) d_bits,
-					       (const uint8_t *) d_voiced, s));
+		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, src_bits(d_bits), (const uint8_t *) d_voiced, s));
 		return 0;
 	});
 }
@@ -3167,7 +3161,7 @@ int melpe_rx_line_dev(melpe_engine *e, void *d_modem_state, void *d_link_state, 
 				e->d_rxmask, voice, count, act, n, j);
 			HIPCHK(hipGetLastError());
 			HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp + (size_t) j * n * MELPE_SF_SAMPLES,
-						       (const uint8_t *) d_bits + (size_t) j * n * MELPE_SF_BYTES,
+						       src_bits((const uint8_t *) d_bits + (size_t) j * n * MELPE_SF_BYTES),
 						       e->d_rxmask, s));
 		}
 		return 0;

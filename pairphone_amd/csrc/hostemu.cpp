@@ -382,6 +382,8 @@ int emu_parse(emu_engine *e, int16_t *par_out, const unsigned char *bits)
 }
 
 #if !defined(MELPE_OPCOUNT)
+}	/* extern "C": a template follows */
+
 /* the two-wave decoder (decoder.h dec2_phase) as k_decode2 runs it: wave A
  * and wave B each on a private copy of the record, phase by phase, the two
  * hand-over buffers the only shared data; each writes back its own side */
@@ -391,7 +393,38 @@ struct HostHb {
 	void put(int k, uint32_t x) const { v[k] = x; }
 };
 
-int emu_decode2(emu_engine *e, int16_t *sp, const unsigned char *bits)
+/* the source of a superframe's parameters, as the kernels' (k_dec.hip BitsIn /
+ * RowsIn): wave A takes channel c's input, wave B's copy of that field is a
+ * pattern -- B never reads the channel or the rows */
+struct HostBits {
+	static constexpr bool ROWS = false;
+	const unsigned char *bits;
+	void take(DecState *A, DecState *B, int c) const
+	{
+		memcpy(A->chbuf, bits + c * 11, 11);
+		memset(B->chbuf, 0xa5, 11);
+	}
+	void done(int, uint8_t) const {}
+};
+
+struct HostRows {
+	static constexpr bool ROWS = true;
+	const int16_t *par;
+	uint8_t *status;
+	void take(DecState *A, DecState *B, int c) const
+	{
+		memcpy(A->par, par + (size_t) c * NF * 30, sizeof(A->par));
+		memset(B->par, 0xa5, sizeof(B->par));
+	}
+	void done(int c, uint8_t st) const
+	{
+		if (status)
+			status[c] = st;
+	}
+};
+
+template <class In>
+static int emu_two(emu_engine *e, int16_t *sp, const In in)
 {
 	static uint32_t hb[2][HB_WORDS];
 	static DecState W[2];
@@ -400,43 +433,31 @@ int emu_decode2(emu_engine *e, int16_t *sp, const unsigned char *bits)
 		memset(hb, 0x5a, sizeof hb);	/* nothing may read a word before it is written */
 		for (int r = 0; r < 2; r++)
 			W[r] = *D;
-		memcpy(W[0].chbuf, bits + c * 11, 11);
-		memset(W[1].chbuf, 0xa5, 11);	/* B never reads the channel */
-		int16_t *out = sp + (size_t) c * BLOCK;
-		for (int p = 0; p < DEC2_PHASES; p++)
-			for (int r = 0; r < 2; r++)
-				dec2_phase(&W[r], out, HostHb{hb[0]}, HostHb{hb[1]}, r, p);
-		memcpy(D, &W[0], DEC_B_BEG);
-		memcpy((char *) D + DEC_B_BEG, (const char *) &W[1] + DEC_B_BEG, sizeof(DecState) - DEC_B_BEG);
-	}
-	return 0;
-}
-
-/* the two-wave synthesis from rows as k_synth_par2 runs it: emu_decode2 with
- * wave A taking and admitting the rows (dec2_phase<Hb, true>); B's copy of
- * par[] is a pattern, it never reads the rows */
-int emu_synth_params2(emu_engine *e, int16_t *sp, const int16_t *par, uint8_t *status)
-{
-	static uint32_t hb[2][HB_WORDS];
-	static DecState W[2];
-	for (int c = 0; c < e->channels; c++) {
-		DecState *D = &e->dec[c];
-		memset(hb, 0x5a, sizeof hb);
-		for (int r = 0; r < 2; r++)
-			W[r] = *D;
-		memcpy(W[0].par, par + (size_t) c * NF * 30, sizeof(W[0].par));
-		memset(W[1].par, 0xa5, sizeof(W[1].par));
+		in.take(&W[0], &W[1], c);
 		uint8_t st = 0;
 		int16_t *out = sp + (size_t) c * BLOCK;
 		for (int p = 0; p < DEC2_PHASES; p++)
 			for (int r = 0; r < 2; r++)
-				dec2_phase<HostHb, true>(&W[r], out, HostHb{hb[0]}, HostHb{hb[1]}, r, p, W[r].par, &st);
+				dec2_phase<HostHb, In::ROWS>(&W[r], out, HostHb{hb[0]}, HostHb{hb[1]}, r, p, W[r].par, &st);
 		memcpy(D, &W[0], DEC_B_BEG);
 		memcpy((char *) D + DEC_B_BEG, (const char *) &W[1] + DEC_B_BEG, sizeof(DecState) - DEC_B_BEG);
-		if (status)
-			status[c] = st;
+		in.done(c, st);
 	}
 	return 0;
+}
+
+extern "C" {
+
+int emu_decode2(emu_engine *e, int16_t *sp, const unsigned char *bits)
+{
+	return emu_two(e, sp, HostBits{bits});
+}
+
+/* the two-wave synthesis from rows as k_synth_par2 runs it: wave A takes and
+ * admits the rows (dec2_phase<Hb, true>) */
+int emu_synth_params2(emu_engine *e, int16_t *sp, const int16_t *par, uint8_t *status)
+{
+	return emu_two(e, sp, HostRows{par, status});
 }
 #endif
 

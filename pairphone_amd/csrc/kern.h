@@ -1,8 +1,8 @@
 /*
  * kern.h -- shared by the translation units that carry the codec: engine.hip,
  * k_npp.hip, k_ana.hip, k_quant.hip, k_ana_mw.hip, k_harm.hip, k_dec.hip, k_r24.hip,
- * k_dsp_eval.hip, k_ana_eval.hip, k_par.hip and k_syn.hip (k_link.hip has no codec tables and
- * includes only launch.h).
+ * k_dsp_eval.hip, k_ana_eval.hip and k_par.hip (k_link.hip has no codec tables and includes
+ * only launch.h).
  *
  * Each TU is compiled separately (in parallel) into its own code object, so
  * each has its own copy of the constant tables (g_tab, g_der: tables.h) and

@@ -26,7 +26,7 @@ struct LinkState;
 /* the translation units that carry their own copy of the constant tables:
  * MELPE_TU(name) in the TU's .hip is the one definition site, this list the
  * one place that names them all (tests/test_abi.py holds the two equal) */
-#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(quant) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(anaeval) X(par) X(syn)
+#define MELPE_TU_LIST(X) X(eng) X(npp) X(ana) X(quant) X(anamw) X(harm) X(dec) X(r24) X(dspeval) X(anaeval) X(par)
 
 extern "C" {
 
@@ -66,12 +66,20 @@ int kl_enc_ana_mw(mlp::EncState *enc, const int16_t *sp, uint8_t *bits, const ui
 		  const int *perm, const int *nlive, uint32_t *lqbuf, AnaGate gate, hipStream_t s);
 size_t kl_enc_ana_mw_lq_words(int n);
 
-/* k_dec.hip */
-int kl_decode(mlp::DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
-	      const int *perm, const int *nlive, hipStream_t s);
-int kl_decode2(mlp::DecState *dec, int16_t *sp, const uint8_t *bits, const uint8_t *active, int n,
-	       const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s);
-size_t kl_decode2_hb_words(int n);
+/* k_dec.hip: the decoder family.  The source of a superframe's parameters
+ * is the channel words (rows 0: in = bits, C x 11) or a tensor of parameter
+ * rows (rows 1: in = C x 3 x 30 int16, read only; status: C bytes or null).
+ * kl_dec runs it with `waves` waves per 64 channels: 1, a lane per channel
+ * (k_decode / k_synth_par), or 2 (k_decode2 / k_synth_par2, through hbuf:
+ * kl_dec2_hb_words(n) dwords, whichever the source). */
+struct DecSrc {
+	int rows;
+	const void *in;
+	uint8_t *status;
+};
+int kl_dec(int waves, DecSrc src, mlp::DecState *dec, int16_t *sp, const uint8_t *active, int n,
+	   const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s);
+size_t kl_dec2_hb_words(int n);
 
 /* k_r24.hip */
 int kl_enc24(mlp::EncState *enc, const int16_t *sp, uint8_t *bits, const uint8_t *active, int n,
@@ -96,14 +104,6 @@ int kl_par_tap(const char *rec, size_t stride, size_t off, uint32_t *par, uint32
 int kl_parse(mlp::DecState *dec, uint32_t *par, const uint8_t *bits, const uint8_t *active, int n,
 	     hipStream_t s);
 
-/* k_syn.hip: the synthesis from parameter rows (par: C x 3 x 30 int16, read
- * only; status: C bytes or null), lane and two-wave forms as the decoder's */
-int kl_synth_par(mlp::DecState *dec, int16_t *sp, const void *par, uint8_t *status, const uint8_t *active,
-		 int n, const int *perm, const int *nlive, hipStream_t s);
-int kl_synth_par2(mlp::DecState *dec, int16_t *sp, const void *par, uint8_t *status, const uint8_t *active,
-		  int n, const int *perm, const int *nlive, uint32_t *hbuf, hipStream_t s);
-size_t kl_synth_par2_hb_words(int n);
-
 /* k_link.hip: the link's packet layer and the Golay sweep */
 int kl_link_tx(LinkState *st, uint8_t *pkts, const uint8_t *voiced, int32_t *ret, const uint8_t *active,
 	       int channels, int packets, hipStream_t s);
@@ -121,20 +121,14 @@ size_t kl_quant_private(void);
 size_t kl_harm_private(void);	/* k_enc_tail, lane per channel */
 size_t kl_harm_wave_private(void);	/* k_enc_harm, wave per channel */
 size_t kl_ana_mw_private(void);
-size_t kl_dec_private(void);
-size_t kl_dec2_private(void);
+size_t kl_dec_private(int waves, int rows);	/* the decoder family's kernel for (waves, DecSrc.rows) */
 size_t kl_parse_private(void);
-size_t kl_syn_private(void);
-size_t kl_syn2_private(void);
 int kl_npp_warm(int n, hipStream_t s);
 int kl_ana_warm(int n, hipStream_t s);
 int kl_quant_warm(int n, hipStream_t s);
 int kl_harm_warm(int n, hipStream_t s);
 int kl_ana_mw_warm(int n, hipStream_t s);
-int kl_dec_warm(int n, hipStream_t s);
-int kl_dec2_warm(int n, hipStream_t s);
-int kl_syn_warm(int n, hipStream_t s);
-int kl_syn2_warm(int n, hipStream_t s);
+int kl_dec_warm(int waves, int rows, int n, hipStream_t s);
 
 }
 

@@ -1,5 +1,5 @@
 """Speech from parameter tensors on the GPU (melpe_synth_params_dev /
-_host, k_syn.hip): against the reference's SKIP_CHANNEL synthesis
+_host, k_dec.hip): against the reference's SKIP_CHANNEL synthesis
 (tests/golden/synpar.json), the reference decoder's goldens (dec_1024.json)
 and the host build of the same device code, every channel and sample.
 
@@ -231,3 +231,97 @@ def test_synth_scratch_is_reserved_at_create():
         torch.cuda.synchronize(dev)
         assert limit() == before
         eng.close()
+
+
+ALT_STEPS = 4       # synth, decode, synth, decode
+
+
+def alternation_case():
+    """One engine serving both sources: 4 superframes on C_GPU channels,
+    steps 0 and 2 the synthesis from the fixture's rows (tiled), steps 1 and 3
+    the decode of the golden bitstreams (tiled), every step under a ragged mask
+    of its own.  Expected values from the host build doing the same, a
+    one-channel engine per channel (its forms take no mask):
+    (rows [2, C, 90], bits [2, C, 11], masks [4, C], pcm [4, C, 540] and
+    status [2, C] with the sentinels where a channel is inactive, melp_par
+    afterwards [C, 90])"""
+    if "alt" not in _cache:
+        vp = ctypes.c_void_p
+        lib = msg.emu()
+        lib.emu_decode.argtypes = [vp, vp, vp]
+        lib.emu_dec_params.argtypes = [vp, ctypes.c_int, vp]
+        src = msg.case_rows()
+        ge = enc_golden()
+        rows = np.ascontiguousarray(np.stack([src[c % msg.C, :2] for c in range(C_GPU)]).transpose(1, 0, 2))
+        gb = np.stack([np.frombuffer(bytes.fromhex(h), np.uint8)[:22] for h in ge["bits_hex"]])
+        bits = np.stack([gb[c % len(gb)] for c in range(C_GPU)]).reshape(C_GPU, 2, 11)
+        bits = np.ascontiguousarray(bits.transpose(1, 0, 2))
+        masks = (np.random.default_rng(29).random((ALT_STEPS, C_GPU)) < 0.6).astype(np.uint8)
+        assert all((masks[a] != masks[b]).any() for a in range(ALT_STEPS) for b in range(a))
+        assert all(0 < masks[k, 192:].sum() < 8 for k in range(ALT_STEPS)), "the tail wave is ragged in every step"
+        pcm = np.full((ALT_STEPS, C_GPU, 540), SENTINEL, np.int16)
+        status = np.full((2, C_GPU), 0x5A, np.uint8)
+        post = np.zeros((C_GPU, 90), np.int16)
+        for c in range(C_GPU):
+            e = lib.emu_create(1)
+            for k in range(ALT_STEPS):
+                if not masks[k, c]:
+                    continue
+                sp = np.zeros(540, np.int16)
+                if k % 2 == 0:
+                    r, st = rows[k // 2, c].copy(), np.full(1, 9, np.uint8)
+                    assert lib.emu_synth_params(e, sp.ctypes.data, r.ctypes.data, st.ctypes.data) == 0
+                    status[k // 2, c] = st[0]
+                else:
+                    b = bits[k // 2, c].copy()
+                    assert lib.emu_decode(e, sp.ctypes.data, b.ctypes.data) == 0
+                pcm[k, c] = sp
+            lib.emu_dec_params(e, 0, post[c].ctypes.data)
+            lib.emu_destroy(e)
+        _cache["alt"] = (rows, bits, masks, pcm, status, post)
+    return _cache["alt"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", [True, False])
+@pytest.mark.parametrize("waves", [1, 2])
+def test_synth_and_decode_alternate_on_one_engine(waves, order):
+    """synth_params_dev and decode_dev superframe by superframe on a single
+    engine of 200 channels (three full waves and 8 lanes: the lane grid's last
+    wave is partial, the two-wave grid's last workgroup holds a full group and
+    an 8-lane one), each call under its own ragged mask: the one BinBuf, the
+    one hand-over buffer and the one launch path serve both sources.  PCM,
+    status bytes and the final melp_par equal the host build's; nothing of an
+    inactive channel is written."""
+    import torch
+    from pairphone_amd import MelpeEngine
+    rows, bits, masks, want_pcm, want_st, want_post = alternation_case()
+    dev = torch.device("cuda", 0)
+    s = torch.cuda.current_stream(dev).cuda_stream
+    d_rows, d_bits, d_masks = (torch.from_numpy(a).to(dev) for a in (rows, bits, masks))
+    d_sp = torch.full((ALT_STEPS, C_GPU, 540), SENTINEL, dtype=torch.int16, device=dev)
+    d_st = torch.full((2, C_GPU), 0x5A, dtype=torch.uint8, device=dev)
+    d_post = torch.zeros((C_GPU, 90), dtype=torch.int16, device=dev)
+    eng = MelpeEngine(C_GPU)
+    eng.set_dec_waves(waves)
+    eng.set_lane_order(order)
+    for k in range(ALT_STEPS):
+        if k % 2 == 0:
+            eng.synth_params_dev(d_sp[k].data_ptr(), d_rows[k // 2].data_ptr(), d_st[k // 2].data_ptr(),
+                                 d_masks[k].data_ptr(), s)
+        else:
+            eng.decode_dev(d_sp[k].data_ptr(), d_bits[k // 2].data_ptr(), d_masks[k].data_ptr(), s)
+    eng.decode_params_dev(d_post.data_ptr(), None, s)
+    torch.cuda.synchronize(dev)
+    eng.close()
+    pcm, st, post = d_sp.cpu().numpy(), d_st.cpu().numpy(), d_post.cpu().numpy()
+    for k in range(ALT_STEPS):
+        off = masks[k] == 0
+        assert (pcm[k, off] == SENTINEL).all(), "step %d: PCM of an inactive channel was written" % k
+        if k % 2 == 0:
+            assert (st[k // 2, off] == 0x5A).all(), "step %d: status of an inactive channel was written" % k
+        bad = sorted(set(np.argwhere(pcm[k] != want_pcm[k])[:, 0].tolist()))
+        assert not bad, "step %d: PCM differs from the host build on %d channels, first %s" % (k, len(bad), bad[:8])
+    assert np.array_equal(st, want_st), "status"
+    bad = sorted(set(np.argwhere(post != want_post)[:, 0].tolist()))
+    assert not bad, "melp_par after the calls differs on %d channels, first %s" % (len(bad), bad[:8])
