@@ -54,6 +54,10 @@ static_assert((160 * 1024 / (MELPE_NPP_WG_WAVES * sizeof(mlp::wv::NppWave) + MTA
 
 using namespace mlp::wv;
 
+/* the lane's min-statistics fields (npp_wave.h NppMinRegs), kept for the
+ * launch: their loads go out ahead of the hot image's, before its first
+ * wait, and their stores follow the image's (wv_min_in / wv_min_out) */
+
 /* melpe_n on `frames` frames per channel; channel c's samples at
  * sp[c*stride ...]; the first call of a channel reads 256 samples (or what
  * the row holds, zero-extended) */
@@ -72,11 +76,14 @@ __global__ __launch_bounds__(NPP_WG) NPP_WPE void k_npp(EncState *enc, int16_t *
 	NppWave &W = Ws[w];
 	WvConst kc;
 	wv_const_init(&kc, lane);
+	NppMinRegs R;
+	wv_min_in(R, &enc[c].npp, lane);
 	wv_state_in(&W, &enc[c].npp, lane);
 	int16_t *x = sp + (size_t) c * stride;
 	for (int f = 0; f < frames; f++)
-		wv_npp_frame(&W, &enc[c].npp, x + f * NPP_HOP, stride - f * NPP_HOP, rate1200 != 0, &kc, lane);
+		wv_npp_frame(&W, &enc[c].npp, R, x + f * NPP_HOP, stride - f * NPP_HOP, rate1200 != 0, &kc, lane);
 	wv_state_out(&enc[c].npp, &W, lane);
+	wv_min_out(&enc[c].npp, R, lane);
 }
 
 /* the NPP part of melpe_a: frames 0..2 of every active channel's 540-sample
@@ -96,11 +103,14 @@ __global__ __launch_bounds__(NPP_WG) NPP_WPE void k_enc_npp(EncState *enc, int16
 	NppWave &W = Ws[w];
 	WvConst kc;
 	wv_const_init(&kc, lane);
+	NppMinRegs R;
+	wv_min_in(R, &enc[c].npp, lane);
 	wv_state_in(&W, &enc[c].npp, lane);
 	int16_t *x = sp + (size_t) c * BLOCK;
 	for (int f = 0; f < NF; f++)
-		wv_npp_frame(&W, &enc[c].npp, x + f * FRAME, BLOCK - f * FRAME, true, &kc, lane);
+		wv_npp_frame(&W, &enc[c].npp, R, x + f * FRAME, BLOCK - f * FRAME, true, &kc, lane);
 	wv_state_out(&enc[c].npp, &W, lane);
+	wv_min_out(&enc[c].npp, R, lane);
 }
 
 static unsigned npp_grid(int n)

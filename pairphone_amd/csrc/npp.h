@@ -613,61 +613,79 @@ MD Word16 npp_noise_slope(const NppState *s)
 /* min_search :889 -- minimum tracking over 8 windows of 9 frames.  Every
  * loop of the reference touches bin i only, so the per-bin part runs each
  * bin through the whole branch; the counters advance afterwards. */
-MD void npp_min_search_bin(NppState *s, NppState *m, int16_t bsp, int16_t bsh, int16_t bsub,
-			   int16_t bsubsh, Word16 slope, int i)
+/* One bin's share of the min-statistics memory that every frame may touch
+ * (the `m` fields of NppState but the ring), as values: the caller loads
+ * them from wherever it keeps them and stores them back. */
+struct NppMinBin {
+	int16_t act_min_sub, act_min_sub_shift;
+	int16_t localflag;
+	int16_t circb_min, circb_min_shift;
+};
+
+/* The minimum search of bin i on values.  `b` is the bin's NppMinBin, read
+ * and updated; act_min / act_min_shift and the noise estimate it leaves
+ * (noisespect, noise_shift, lambdaD, lambdaD_shift) are bin i's fields of
+ * `s`, as before.  The ring enters only when minspec_counter == 0: ring[k] /
+ * ring_sh[k] are circb[k][i] / circb_shift[k][i] as they stand before this
+ * frame (neither is read on other frames), and the entry at circb_index is
+ * taken from act_min as the reference writes it before its scan.  The caller
+ * then writes the ring: on `true` all eight entries := b.circb_min /
+ * b.circb_min_shift, otherwise (and only when minspec_counter == 0) the
+ * entry at circb_index := act_min[i] / act_min_shift[i]. */
+MD bool npp_min_search_val(NppState *s, NppMinBin &b, const int16_t *ring, const int16_t *ring_sh,
+			   int16_t bsp, int16_t bsh, int16_t bsub, int16_t bsubsh, Word16 slope, int i)
 {
+	bool fill = false;
 	if (s->minspec_counter == 0) {
 		if (cmp_shift(bsp, bsh, s->act_min[i], s->act_min_shift[i]) < 0) {
 			s->act_min[i] = bsp;
 			s->act_min_shift[i] = bsh;
-			m->act_min_sub[i] = bsub;
-			m->act_min_sub_shift[i] = bsubsh;
-			m->localflag[i] = 0;
+			b.act_min_sub = bsub;
+			b.act_min_sub_shift = bsubsh;
+			b.localflag = 0;
 		}
-		m->circb[s->circb_index][i] = s->act_min[i];
-		m->circb_shift[s->circb_index][i] = s->act_min_shift[i];
-		Word16 t1 = m->circb[0][i], t2 = m->circb_shift[0][i];
-		for (int k = 1; k < NPP_NMINWIN; k++)
-			if (cmp_shift(m->circb[k][i], m->circb_shift[k][i], t1, t2) < 0) {
-				t1 = m->circb[k][i];
-				t2 = m->circb_shift[k][i];
-			}
-		m->circb_min[i] = t1;
-		m->circb_min_shift[i] = t2;
-		Word16 t = mult(slope, m->circb_min[i]);
-		Word16 ts = add(m->circb_min_shift[i], 4);
-		if (m->localflag[i] &&
-		    cmp_shift(m->act_min_sub[i], m->act_min_sub_shift[i],
-			      m->circb_min[i], m->circb_min_shift[i]) > 0 &&
-		    cmp_shift(m->act_min_sub[i], m->act_min_sub_shift[i], t, ts) < 0) {
-			m->circb_min[i] = m->act_min_sub[i];
-			m->circb_min_shift[i] = m->act_min_sub_shift[i];
-			for (int k = 0; k < NPP_NMINWIN; k++) {
-				m->circb[k][i] = m->circb_min[i];
-				m->circb_shift[k][i] = m->circb_min_shift[i];
+		const int ci = s->circb_index;
+		Word16 t1 = ci == 0 ? s->act_min[i] : ring[0];
+		Word16 t2 = ci == 0 ? s->act_min_shift[i] : ring_sh[0];
+		for (int k = 1; k < NPP_NMINWIN; k++) {
+			Word16 r1 = ci == k ? s->act_min[i] : ring[k];
+			Word16 r2 = ci == k ? s->act_min_shift[i] : ring_sh[k];
+			if (cmp_shift(r1, r2, t1, t2) < 0) {
+				t1 = r1;
+				t2 = r2;
 			}
 		}
-		m->localflag[i] = 0;
+		b.circb_min = t1;
+		b.circb_min_shift = t2;
+		Word16 t = mult(slope, b.circb_min);
+		Word16 ts = add(b.circb_min_shift, 4);
+		if (b.localflag &&
+		    cmp_shift(b.act_min_sub, b.act_min_sub_shift, b.circb_min, b.circb_min_shift) > 0 &&
+		    cmp_shift(b.act_min_sub, b.act_min_sub_shift, t, ts) < 0) {
+			b.circb_min = b.act_min_sub;
+			b.circb_min_shift = b.act_min_sub_shift;
+			fill = true;
+		}
+		b.localflag = 0;
 	} else if (s->minspec_counter == 1) {
 		s->act_min[i] = bsp;
 		s->act_min_shift[i] = bsh;
-		m->act_min_sub[i] = bsub;
-		m->act_min_sub_shift[i] = bsubsh;
+		b.act_min_sub = bsub;
+		b.act_min_sub_shift = bsubsh;
 	} else {
 		if (cmp_shift(bsp, bsh, s->act_min[i], s->act_min_shift[i]) < 0) {
 			s->act_min[i] = bsp;
 			s->act_min_shift[i] = bsh;
-			m->act_min_sub[i] = bsub;
-			m->act_min_sub_shift[i] = bsubsh;
-			m->localflag[i] = 1;
+			b.act_min_sub = bsub;
+			b.act_min_sub_shift = bsubsh;
+			b.localflag = 1;
 		}
-		if (cmp_shift(m->act_min_sub[i], m->act_min_sub_shift[i],
-			      m->circb_min[i], m->circb_min_shift[i]) < 0) {
-			m->circb_min[i] = m->act_min_sub[i];
-			m->circb_min_shift[i] = m->act_min_sub_shift[i];
+		if (cmp_shift(b.act_min_sub, b.act_min_sub_shift, b.circb_min, b.circb_min_shift) < 0) {
+			b.circb_min = b.act_min_sub;
+			b.circb_min_shift = b.act_min_sub_shift;
 		}
-		s->noisespect[i] = m->circb_min[i];
-		s->noise_shift[i] = m->circb_min_shift[i];
+		s->noisespect[i] = b.circb_min;
+		s->noise_shift[i] = b.circb_min_shift;
 		Word32 L = L_mult(NOISE_BIAS, s->noisespect[i]);
 		if (L < 0x40000000L) {
 			L = L_shl(L, 1);
@@ -677,6 +695,42 @@ MD void npp_min_search_bin(NppState *s, NppState *m, int16_t bsp, int16_t bsh, i
 		}
 		s->lambdaD[i] = extract_h(L);
 	}
+	return fill;
+}
+
+/* the ring after npp_min_search_val, in the record `m` */
+MD void npp_min_ring_store(const NppState *s, NppState *m, const NppMinBin &b, bool fill, int i)
+{
+	if (fill) {
+		for (int k = 0; k < NPP_NMINWIN; k++) {
+			m->circb[k][i] = b.circb_min;
+			m->circb_shift[k][i] = b.circb_min_shift;
+		}
+	} else if (s->minspec_counter == 0) {
+		m->circb[s->circb_index][i] = s->act_min[i];
+		m->circb_shift[s->circb_index][i] = s->act_min_shift[i];
+	}
+}
+
+/* the same with the loads and stores around it: bin i of the record `m` */
+MD void npp_min_search_bin(NppState *s, NppState *m, int16_t bsp, int16_t bsh, int16_t bsub,
+			   int16_t bsubsh, Word16 slope, int i)
+{
+	NppMinBin b = {m->act_min_sub[i], m->act_min_sub_shift[i], m->localflag[i], m->circb_min[i],
+		       m->circb_min_shift[i]};
+	int16_t ring[NPP_NMINWIN] = {0}, ring_sh[NPP_NMINWIN] = {0};
+	if (s->minspec_counter == 0)
+		for (int k = 0; k < NPP_NMINWIN; k++) {
+			ring[k] = m->circb[k][i];
+			ring_sh[k] = m->circb_shift[k][i];
+		}
+	bool fill = npp_min_search_val(s, b, ring, ring_sh, bsp, bsh, bsub, bsubsh, slope, i);
+	npp_min_ring_store(s, m, b, fill, i);
+	m->act_min_sub[i] = b.act_min_sub;
+	m->act_min_sub_shift[i] = b.act_min_sub_shift;
+	m->localflag[i] = b.localflag;
+	m->circb_min[i] = b.circb_min;
+	m->circb_min_shift[i] = b.circb_min_shift;
 }
 
 MD void npp_min_search_post(NppState *s)

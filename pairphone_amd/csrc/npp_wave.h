@@ -349,22 +349,90 @@ MD void wv_mirror(int16_t *yb, int lane)
 	wsync();
 }
 
-/* minstat_init :1164 */
-MD void wv_minstat_init(NppState *s, NppState *m, int lane)
+/* The lane's share of the min-statistics memory that every frame may touch:
+ * the five per-frame fields (NppMinBin) of its bins lane + 64 t, two int16
+ * to a register and localflag as bit t.  Nobody but the lane reads or writes
+ * those 15 values, so they are loaded from the HBM record once (wv_min_in),
+ * kept here and written back once (wv_min_out); only the ring stays behind
+ * in the record, read on the one frame in nine that scans it.  localflag
+ * is written back as 0 or 1, the only values the codec ever stores in it
+ * (records stay interchangeable with ones that keep the fields in HBM). */
+struct NppMinRegs {
+	unsigned sub[3];	/* act_min_sub | act_min_sub_shift << 16 */
+	unsigned cmin[3];	/* circb_min | circb_min_shift << 16 */
+	unsigned flag;		/* localflag of bin lane + 64 t in bit t */
+};
+
+/* The min-statistics part of a channel's record as a buffer: the record's
+ * address is wave-uniform, so it sits in a descriptor (four scalar
+ * registers, bounds = that part of the record) and an access is the
+ * descriptor plus a 32-bit lane offset plus a constant -- no per-lane 64-bit
+ * address to keep across the frame, and none for the compiler to hoist out
+ * of the frame loop and spill. */
+typedef __amdgpu_buffer_rsrc_t MinRec;
+MD MinRec wv_min_rec(const NppState *m)
 {
-	LANE_LOOP(i, NPP_NB) {
+	return __builtin_amdgcn_make_buffer_rsrc((char *) const_cast<NppState *>(m) + NPP_HOT_BYTES, 0,
+						 (int) (sizeof(NppState) - NPP_HOT_BYTES), 0x00020000);
+}
+/* byte offsets into it: a field of bin lane + 64 t; entry k of a ring */
+#define MOFF(lane, t, field) (2 * (lane) + (int) (offsetof(NppState, field) - NPP_HOT_BYTES + 2 * WV * (t)))
+#define MRING_OFF(lane, t, field, k) (MOFF(lane, t, field) + (int) ((k) * NPP_NB * sizeof(int16_t)))
+__device__ __forceinline__ int16_t mld(MinRec r, int off, int soff = 0)
+{
+	return (int16_t) __builtin_amdgcn_raw_buffer_load_b16(r, off, soff, 0);
+}
+__device__ __forceinline__ void mst(MinRec r, int off, int16_t v, int soff = 0)
+{
+	__builtin_amdgcn_raw_buffer_store_b16(v, r, off, soff, 0);
+}
+
+__device__ __forceinline__ unsigned pack16(int16_t lo, int16_t hi)
+{
+	return (unsigned) (uint16_t) lo | (unsigned) (uint16_t) hi << 16;
+}
+
+MD void wv_min_in(NppMinRegs &R, const NppState *m, int lane)
+{
+	const MinRec r = wv_min_rec(m);
+	R.flag = 0;
+	_Pragma("unroll") for (int t = 0; t < 3; t++)
+		R.sub[t] = R.cmin[t] = 0;
+	BIN_PASSES(t, i, {
+		R.sub[t] = pack16(mld(r, MOFF(lane, t, act_min_sub)), mld(r, MOFF(lane, t, act_min_sub_shift)));
+		R.cmin[t] = pack16(mld(r, MOFF(lane, t, circb_min)), mld(r, MOFF(lane, t, circb_min_shift)));
+		R.flag |= (unsigned) (mld(r, MOFF(lane, t, localflag)) != 0) << t;
+	})
+}
+
+MD void wv_min_out(NppState *m, const NppMinRegs &R, int lane)
+{
+	const MinRec r = wv_min_rec(m);
+	BIN_PASSES(t, i, {
+		mst(r, MOFF(lane, t, act_min_sub), (int16_t) R.sub[t]);
+		mst(r, MOFF(lane, t, act_min_sub_shift), (int16_t) (R.sub[t] >> 16));
+		mst(r, MOFF(lane, t, circb_min), (int16_t) R.cmin[t]);
+		mst(r, MOFF(lane, t, circb_min_shift), (int16_t) (R.cmin[t] >> 16));
+		mst(r, MOFF(lane, t, localflag), (int16_t) (R.flag >> t & 1));
+	})
+}
+
+/* minstat_init :1164 */
+MD void wv_minstat_init(NppState *s, NppState *m, NppMinRegs &R, int lane)
+{
+	const MinRec r = wv_min_rec(m);
+	BIN_PASSES(t, i, {
 		Word16 sp = mult(s->lambdaD[i], NOISE_BIAS);
 		Word16 ls = s->lambdaD_shift[i];
 		s->smoothedspect[i] = sp;
 		for (int k = 0; k < NPP_NMINWIN; k++) {
-			m->circb[k][i] = sp;
-			m->circb_shift[k][i] = ls;
+			mst(r, MRING_OFF(lane, t, circb, k), sp);
+			mst(r, MRING_OFF(lane, t, circb_shift, k), ls);
 		}
 		s->sm_shift[i] = ls;
 		s->act_min[i] = sp;
 		s->act_min_shift[i] = ls;
-		m->act_min_sub[i] = sp;
-		m->act_min_sub_shift[i] = ls;
+		R.sub[t] = pack16(sp, ls);	/* the register copies are live here */
 		s->noisespect[i] = sp;
 		s->noise_shift[i] = ls;
 		s->var_sp_av[i] = mult(sp, 20066);
@@ -373,12 +441,12 @@ MD void wv_minstat_init(NppState *s, NppState *m, int lane)
 		Word16 sh = norm_l(L);
 		s->var_sp_2[i] = extract_h(L_shl(L, sh));
 		s->av2_shift[i] = sub(shl(ls, 1), sub(sh, 1));
-	}
+	})
 	s->alphacorr = 29491;
 }
 
 /* enh_init :1023 -- initial noise estimate; `noise` (256, LDS) is consumed */
-MD void wv_enh_init(NppWave *W, int16_t *noise, const WvConst *kc, int lane, NppState *m)
+MD void wv_enh_init(NppWave *W, int16_t *noise, const WvConst *kc, int lane, NppState *m, NppMinRegs &R)
 {
 	NppState *s = wv_S(W);
 	int16_t *yb = W->w.ybuf;
@@ -470,7 +538,7 @@ MD void wv_enh_init(NppWave *W, int16_t *noise, const WvConst *kc, int lane, Npp
 	s->n_pwr_shift = sub(add(nsh, 1), sh);
 	s->SN_LT = divide_s(14648, s->n_pwr);
 	s->SN_LT_shift = sub(22, s->n_pwr_shift);
-	wv_minstat_init(s, m, lane);
+	wv_minstat_init(s, m, R, lane);
 	wsync();
 }
 
@@ -641,8 +709,8 @@ MD void wv_gain_scan(const int16_t *gk, const int16_t *gks, int lane, Word16 *ga
 
 /* process_frame :1212 -- one 256-sample analysis/synthesis frame; in and
  * out are 256-sample LDS buffers */
-MD void wv_process_frame(NppWave *W, NppState *m, const int16_t *in, int16_t *out, const WvConst *kc,
-			 int lane)
+MD void wv_process_frame(NppWave *W, NppState *m, NppMinRegs &R, const int16_t *in, int16_t *out,
+			 const WvConst *kc, int lane)
 {
 	PROF_SCOPE(34);
 	NppState *s = wv_S(W);
@@ -767,12 +835,40 @@ MD void wv_process_frame(NppWave *W, NppState *m, const int16_t *in, int16_t *ou
 	Word16 f1, f2;
 	Word16 vsq = npp_bias_scalars(s, w, vsum, &f1, &f2);
 	Word16 slope = npp_noise_slope(s);
+	/* wave-uniform, and known to be: the ring's loads and its one store sit
+	 * in scalar control flow */
+	const bool ring_frame = __builtin_amdgcn_readfirstlane((int) s->minspec_counter) == 0;
+	const int ring_at = __builtin_amdgcn_readfirstlane((int) s->circb_index) * (int) (NPP_NB * sizeof(int16_t));
+	const MinRec r = wv_min_rec(m);
 	{
 	PROF_SCOPE(55);
 	BIN_PASSES(t, i, {
 		int16_t bsp, bsh, bsub, bsubsh;	/* bin i's, this lane's only */
+		/* the ring's 16 values of bin i, asked for before the bias pass
+		 * whose arithmetic their latency hides behind */
+		int16_t ring[NPP_NMINWIN] = {0}, ring_sh[NPP_NMINWIN] = {0};
+		if (ring_frame) {
+			_Pragma("unroll") for (int k = 0; k < NPP_NMINWIN; k++) {
+				ring[k] = mld(r, MRING_OFF(lane, t, circb, k));
+				ring_sh[k] = mld(r, MRING_OFF(lane, t, circb_shift, k));
+			}
+		}
 		npp_bias2_bin(s, w, bsp, bsh, bsub, bsubsh, vsq, f1, f2, i);
-		npp_min_search_bin(s, m, bsp, bsh, bsub, bsubsh, slope, i);
+		NppMinBin b = {(int16_t) R.sub[t], (int16_t) (R.sub[t] >> 16), (int16_t) (R.flag >> t & 1),
+			       (int16_t) R.cmin[t], (int16_t) (R.cmin[t] >> 16)};
+		bool fill = npp_min_search_val(s, b, ring, ring_sh, bsp, bsh, bsub, bsubsh, slope, i);
+		if (fill) {
+			_Pragma("unroll") for (int k = 0; k < NPP_NMINWIN; k++) {
+				mst(r, MRING_OFF(lane, t, circb, k), b.circb_min);
+				mst(r, MRING_OFF(lane, t, circb_shift, k), b.circb_min_shift);
+			}
+		} else if (ring_frame) {
+			mst(r, MRING_OFF(lane, t, circb, 0), s->act_min[i], ring_at);
+			mst(r, MRING_OFF(lane, t, circb_shift, 0), s->act_min_shift[i], ring_at);
+		}
+		R.sub[t] = pack16(b.act_min_sub, b.act_min_sub_shift);
+		R.cmin[t] = pack16(b.circb_min, b.circb_min_shift);
+		R.flag = (R.flag & ~(1u << t)) | (unsigned) (b.localflag != 0) << t;
 		gk[i] = divide_s(shr(w->YY[i], 1), s->lambdaD[i]);
 		gks[i] = sub(add(w->YY_shift[i], 1), s->lambdaD_shift[i]);
 	})
@@ -946,8 +1042,8 @@ MD void wv_process_frame(NppWave *W, NppState *m, const int16_t *in, int16_t *ou
 /* npp :170 -- 180 new samples from `x` (global memory), 180 enhanced
  * samples back to the same place.  `avail` = valid samples at x for the
  * first call's 256-sample read (npp.c:176-189); short reads see zeros. */
-MD void wv_npp_frame(NppWave *W, NppState *m, int16_t *x, int avail, bool rate1200, const WvConst *kc,
-		     int lane)
+MD void wv_npp_frame(NppWave *W, NppState *m, NppMinRegs &R, int16_t *x, int avail, bool rate1200,
+		     const WvConst *kc, int lane)
 {
 	PROF_SCOPE(0);
 	NppState *s = wv_S(W);
@@ -962,7 +1058,7 @@ MD void wv_npp_frame(NppWave *W, NppState *m, int16_t *x, int avail, bool rate12
 			noise[i] = v;
 		}
 		wsync();
-		wv_enh_init(W, noise, kc, lane, m);
+		wv_enh_init(W, noise, kc, lane, m, R);
 		LANE_LOOP(i, NPP_WIN)
 			s->speech_in[i] = 0;
 		s->started = 1;
@@ -974,7 +1070,7 @@ MD void wv_npp_frame(NppWave *W, NppState *m, int16_t *x, int avail, bool rate12
 	LANE_LOOP(i, NPP_HOP)
 		s->speech_in[NPP_OVL + i] = x[i];
 	wsync();
-	wv_process_frame(W, m, s->speech_in, W->buf, kc, lane);
+	wv_process_frame(W, m, R, s->speech_in, W->buf, kc, lane);
 	LANE_LOOP(i, NPP_OVL) {
 		Word16 o = add(W->buf[i], s->overlap[i]);
 		s->overlap[i] = W->buf[NPP_HOP + i];
@@ -986,14 +1082,26 @@ MD void wv_npp_frame(NppWave *W, NppState *m, int16_t *x, int avail, bool rate12
 	wsync();
 }
 
-/* HBM record <-> LDS image of a channel's NppState, dword copies */
+/* HBM record <-> LDS image of a channel's NppState: the record side in
+ * 16-byte pieces (6 accesses per lane for the 5,600 bytes instead of 22; the
+ * records are 16-byte multiples at 16-byte aligned addresses), may_alias
+ * like kern.h's dwords.  Measured against dword copies: 31.18 -> 30.81 ms per
+ * step at 262,144 channels, below it in every run (profiles/r09_minstat_ab.txt) */
+typedef uint32_t u32x4_alias __attribute__((ext_vector_type(4), may_alias, aligned(16)));
+static_assert(NPP_HOT_BYTES % 16 == 0 && sizeof(EncState) % 16 == 0 && offsetof(EncState, npp) % 16 == 0,
+	      "NppState hot part copied in 16-byte pieces");
 MD void wv_state_in(NppWave *W, const NppState *g, int lane)
 {
 	PROF_SCOPE(35);
-	const u32_alias *src = (const u32_alias *) g;	/* kern.h: may_alias dwords */
-	u32_alias *dst = W->s_hot;
-	LANE_LOOP(i, (int) (NPP_HOT_BYTES / 4))
-		dst[i] = src[i];
+	const u32x4_alias *src = (const u32x4_alias *) g;
+	u32_alias *dst = W->s_hot;	/* 4-byte aligned in LDS: written by dwords */
+	LANE_LOOP(i, (int) (NPP_HOT_BYTES / 16)) {
+		u32x4_alias v = src[i];
+		dst[4 * i] = v.x;
+		dst[4 * i + 1] = v.y;
+		dst[4 * i + 2] = v.z;
+		dst[4 * i + 3] = v.w;
+	}
 	wsync();
 }
 
@@ -1002,9 +1110,15 @@ MD void wv_state_out(NppState *g, const NppWave *W, int lane)
 	PROF_SCOPE(35);
 	wsync();
 	const u32_alias *src = W->s_hot;
-	u32_alias *dst = (u32_alias *) g;
-	LANE_LOOP(i, (int) (NPP_HOT_BYTES / 4))
-		dst[i] = src[i];
+	u32x4_alias *dst = (u32x4_alias *) g;
+	LANE_LOOP(i, (int) (NPP_HOT_BYTES / 16)) {
+		u32x4_alias v;
+		v.x = src[4 * i];
+		v.y = src[4 * i + 1];
+		v.z = src[4 * i + 2];
+		v.w = src[4 * i + 3];
+		dst[i] = v;
+	}
 }
 
 }  // namespace wv
