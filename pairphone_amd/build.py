@@ -58,7 +58,7 @@ PROF_LIB = os.path.join(ROOT, "pairphone_amd", "libmelpe_amd_prof.so")
 
 
 TUS = ("engine", "k_npp", "k_ana", "k_quant", "k_ana_mw", "k_harm", "k_dec", "k_r24", "k_dsp_eval", "k_ana_eval",
-       "k_par", "k_link")
+       "k_par", "k_link", "k_line", "k_state")
 # the codec TUs compile their whole call tree inline, so every access to a
 # lane's private state is a scratch_/global_ instruction with counted waits
 # instead of a generic FLAT access; this is what costs compile
@@ -121,6 +121,9 @@ def device_disassembly(obj, arch=None):
     import tempfile
     with tempfile.TemporaryDirectory() as tmp:
         fat, elf = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.elf")
+        secs = subprocess.run(["objdump", "-h", obj], check=True, capture_output=True, text=True).stdout
+        if ".hip_fatbin" not in secs:	# no bundle: a TU without device code (engine.hip)
+            return {}
         subprocess.run(["objcopy", "--dump-section", ".hip_fatbin=" + fat, obj], check=True)
         for a in dict.fromkeys((arch, "gfx950")):	# an A/B build may mix targets
             r = subprocess.run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "--unbundle", "--type=o",

@@ -1,22 +1,26 @@
 /*
  * engine.hip -- host side of the MI355X MELPe-1200 engine: the C ABI
- * (include/melpe.h drop-in, include/melpe_batch.h batched), device table
- * upload, and the kernels that are not the codec's: reset, init, parameter
- * sharing, the synthetic test-signal generator, voice crypt, the VAD, the
- * VAD-framed stream format, the modem, the lane-order sort and the
- * basic-op / helper evaluators of the parity tests.
+ * (include/melpe.h drop-in, include/melpe_batch.h batched), the engine
+ * object, stream and event plumbing, staging for the host calls, and device
+ * table upload.  Host code only: this file defines no kernel and launches
+ * none itself.
  *
- * The codec kernels live in their own translation units, compiled in
- * parallel (pairphone_amd/build.py) and linked into libmelpe_amd.so:
- *   k_npp.hip  melpe_n, and the NPP half of melpe_a (melpe/melpe.c:94-96)
- *   k_ana.hip  the analysis half of melpe_a (melpe/melpe.c:97-98)
- *   k_dec.hip  melpe_s (melpe/melpe.c:102-107), and the synthesis from
- *              parameter rows
+ * Every kernel lives in a k_*.hip translation unit next to its kl_*
+ * launcher, compiled in parallel (pairphone_amd/build.py) and linked into
+ * libmelpe_amd.so:
+ *   k_npp.hip    melpe_n, and the NPP half of melpe_a (melpe/melpe.c:94-96)
+ *   k_ana.hip    the analysis half of melpe_a (melpe/melpe.c:97-98)
+ *   k_dec.hip    melpe_s (melpe/melpe.c:102-107), and the synthesis from
+ *                parameter rows
+ *   k_state.hip  reset, init, parameter sharing, the test-signal generator
+ *                and the lane-order sort
+ *   k_line.hip   voice crypt, the VAD, the VAD-framed stream format, the
+ *                modem and the receive loop
  * and the rest that kern.h lists; launch.h declares what this file calls in
  * them.
  * Execution model: one lane per channel (kern.h).  Per-channel
- * state lives in HBM (EncState / DecState), the codebooks in each TU's
- * constant tables (uploaded once per device).
+ * state lives in HBM (EncState / DecState), the codebooks in the constant
+ * tables of each TU whose kernels read them (uploaded once per device).
  */
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -29,16 +33,13 @@
 #include <vector>
 
 #include "kern.h"
-#define SYN_FN __host__ __device__ static inline
 #include "synth.h"
 #include "voice_crypt.h"
 #include "vad.h"
 #include "stream_fmt.h"
 #include "ops_eval.h"
-#include "helpers_eval.h"
 #include "dsp_eval_modes.h"
 #include "ana_eval_modes.h"
-#define MODEM_FN __host__ __device__ static inline
 #include "modem.h"
 #include "rxline.h"
 #include "../../include/melpe.h"
@@ -59,609 +60,6 @@ __asm__(".section .rodata\n"
 #endif
 extern "C" const unsigned char melpe_tables_blob[];
 extern "C" const unsigned char melpe_tables_blob_end[];
-
-MELPE_TU(eng)
-
-/* ------------------------------------------------------------------ */
-/* small kernels: reset, init, parameter sharing, test-signal synth   */
-/* ------------------------------------------------------------------ */
-
-__global__ __launch_bounds__(WAVE) void k_reset(EncState *enc, DecState *dec,
-						 const uint8_t *mask, int n, int which)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= n || (mask && !mask[c]))
-		return;
-	if (which & 1)
-		enc_reset(&enc[c]);
-	if (which & 2)
-		dec_reset(&dec[c]);
-}
-
-/* melpe_i on channel 0 of the single-stream engine: melp_ana_init +
- * melp_syn_init (melpe/melpe.c:72-88) */
-__global__ void k_melpe_i(EncState *enc, DecState *dec)
-{
-	if (threadIdx.x == 0) {
-		enc_melpe_i(&enc->a);
-		dec_melpe_i(dec);
-	}
-}
-
-/* The reference's analysis and synthesis share melp_par, quant_par and chbuf
- * (melpe/global.c:27-39).  For the single-stream drop-in the engine keeps
- * them in EncState and hands them to the decoder around each melpe_s, so an
- * interleaved melpe_a / melpe_s sequence sees exactly the reference's
- * process-global state.  dir 0: encoder -> decoder, 1: decoder -> encoder. */
-__global__ void k_share_params(EncState *enc, DecState *dec, int dir)
-{
-	if (threadIdx.x != 0)
-		return;
-	EncAna *a = &enc->a;
-	if (dir == 0) {
-		for (int i = 0; i < NF; i++)
-			dec->par[i] = a->par[i];
-		dec->qpar = a->qpar;
-	} else {
-		for (int i = 0; i < NF; i++)
-			a->par[i] = dec->par[i];
-		a->qpar = dec->qpar;
-		for (int k = 0; k < 11; k++)
-			a->chbuf[k] = dec->chbuf[k];
-	}
-}
-
-__global__ __launch_bounds__(WAVE) void k_synth_seed(synth_state *s, uint32_t seed,
-						      uint32_t ch0, int n)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c < n)
-		synth_init(&s[c], synth_mix(seed, ch0 + (uint32_t) c));
-}
-
-__global__ __launch_bounds__(WAVE) void k_synth(synth_state *s, int16_t *out, int samples, int n)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= n)
-		return;
-	synth_state st = s[c];
-	synth_block(&st, out + (size_t) c * samples, samples);
-	s[c] = st;
-}
-
-
-/* VoiceEnc / VoiceDec (crp.c:986-1027, voice_crypt.h), one lane per packet:
- * packet k of channel c is pkts[(c*K + k)*11 ..], its counter counters[c] + k
- * (cnt_out / cnt_in advance by one per packet, crp.c:805), its key the
- * channel's 16 bytes keys[c*16 ..] */
-__global__ __launch_bounds__(256) void k_voice_crypt(unsigned char *pkts, const uint32_t *counters,
-						     const uint4 *keys, const uint8_t *invert,
-						     int channels, int packets, int dir)
-{
-	long i = blockIdx.x * (long) blockDim.x + threadIdx.x;
-	if (i >= (long) channels * packets)
-		return;
-	int c = (int) (i / packets), k = (int) (i - (long) c * packets);
-	uint4 kv = keys[c];
-	uint32_t key[4] = {kv.x, kv.y, kv.z, kv.w};
-	unsigned char *p = pkts + i * VC_PKT_BYTES;
-	unsigned char b[VC_PKT_BYTES];
-#pragma unroll
-	for (int j = 0; j < VC_PKT_BYTES; j++)
-		b[j] = p[j];
-	vc_apply(b, counters[c] + (uint32_t) k, key, dir, invert ? invert[c] : 0);
-#pragma unroll
-	for (int j = 0; j < VC_PKT_BYTES; j++)
-		p[j] = b[j];
-}
-
-
-/* VAD of one superframe per channel (vad.h): the six vad2 windows of
- * tx.c:234-239 on the channel's 540 samples; votes[c] = their sum */
-__global__ __launch_bounds__(WAVE) void k_vad(VadState *st, const int16_t *sp, uint8_t *votes,
-					      uint8_t *gate, const uint8_t *active, int channels)
-{
-	int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= channels)
-		return;
-	if (active && !active[c]) {
-		if (gate)
-			gate[c] = 0;
-		return;
-	}
-	VadState s = st[c];
-	int n = va_superframe(sp + (size_t) c * MELPE_SF_SAMPLES, &s);
-	st[c] = s;
-	votes[c] = (uint8_t) n;
-	if (gate)	/* tx.c:242-244: encoded when any window voted */
-		gate[c] = n > 0;
-}
-
-__global__ __launch_bounds__(WAVE) void k_vad_reset(VadState *st, const uint8_t *mask, int channels)
-{
-	int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c >= channels || (mask && !mask[c]))
-		return;
-	VadState z;
-	memset(&z, 0, sizeof z);
-	st[c] = z;
-}
-
-/*
- * The VAD-framed stream format on the device (stream_fmt.h).
- *
- * melpe_stream_pack_dev compacts one superframe's frames across channels:
- * channel c's frame of len(c) = 11, 1 or 0 bytes goes to out[offs[c] ..],
- * offs = the exclusive prefix sum of len.  The scan is three launches, so no
- * workgroup ever waits for another: k_stream_len writes each block's total
- * to work[], k_stream_scan (one block) turns work[] into the blocks' bases,
- * tile after tile of STREAM_BLOCK totals with a running carry, and
- * k_stream_scatter scans its block again, adds the block's base and writes
- * the frames.  Lengths are recomputed from votes and active in both passes,
- * not stored.
- */
-#define STREAM_BLOCK 256
-static_assert(STREAM_BLOCK % WAVE == 0 && WAVE == 64, "the scans below are written for wave64");
-
-/* inclusive prefix sum over the wave's 64 lanes, on the DPP lane network:
- * row_shr:1,2,4,8 scan each row of 16 lanes (bound_ctrl: a lane shifted in
- * from outside the row reads 0), row_bcast:15 adds a row's total to the next
- * row (rows 1 and 3), row_bcast:31 adds the lower half's total to rows 2 and
- * 3.  Every lane of the wave must be active. */
-__device__ static inline unsigned wave_scan_incl(unsigned v)
-{
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x111, 0xf, 0xf, true);
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x112, 0xf, 0xf, true);
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x114, 0xf, 0xf, true);
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x118, 0xf, 0xf, true);
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x142, 0xa, 0xf, false);
-	v += (unsigned) __builtin_amdgcn_update_dpp(0, (int) v, 0x143, 0xc, 0xf, false);
-	return v;
-}
-
-/* exclusive prefix sum of v over the block's STREAM_BLOCK lanes, *total =
- * their sum; called by every lane of the block.  A caller that loops
- * synchronises the block before the next call (wsum is reused). */
-__device__ static inline unsigned block_scan_excl(unsigned v, unsigned *total)
-{
-	__shared__ unsigned wsum[STREAM_BLOCK / WAVE];
-	const unsigned inc = wave_scan_incl(v);
-	const int w = threadIdx.x / WAVE;
-	if ((threadIdx.x & (WAVE - 1)) == WAVE - 1)
-		wsum[w] = inc;
-	__syncthreads();
-	unsigned base = 0, t = 0;
-#pragma unroll
-	for (int k = 0; k < STREAM_BLOCK / WAVE; k++) {
-		const unsigned s = wsum[k];
-		base += k < w ? s : 0u;
-		t += s;
-	}
-	*total = t;
-	return base + inc - v;
-}
-
-__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_len(const uint8_t *votes, const uint8_t *active,
-							     uint32_t *work, int channels)
-{
-	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
-	const unsigned len = c < channels ? sfmt_frame_len(!active || active[c], votes[c]) : 0u;
-	unsigned total;
-	block_scan_excl(len, &total);
-	if (threadIdx.x == 0)
-		work[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_scan(uint32_t *work, unsigned nb)
-{
-	unsigned carry = 0;
-	for (unsigned t0 = 0; t0 < nb; t0 += STREAM_BLOCK) {	/* uniform: every lane runs every tile */
-		const unsigned i = t0 + threadIdx.x;
-		const unsigned v = i < nb ? work[i] : 0u;
-		unsigned total;
-		const unsigned ex = block_scan_excl(v, &total);
-		if (i < nb)
-			work[i] = carry + ex;
-		carry += total;
-		__syncthreads();
-	}
-}
-
-__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_scatter(const unsigned char *bits, const uint8_t *votes,
-								 uint8_t *last, unsigned char *out, uint32_t *offs,
-								 const uint32_t *work, int channels,
-								 const uint8_t *active)
-{
-	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
-	const bool in = c < channels;
-	const unsigned vote = in ? votes[c] : 0u;
-	const unsigned len = in ? sfmt_frame_len(!active || active[c], vote) : 0u;
-	unsigned total;
-	const unsigned off = work[blockIdx.x] + block_scan_excl(len, &total);
-	if (!in)
-		return;
-	offs[c] = off;
-	if (c == channels - 1)
-		offs[channels] = off + len;
-	if (len)	/* off + len <= the total <= channels * 11, out's capacity */
-		last[c] = sfmt_pack(bits + c * SFMT_BYTES, vote, last[c], out + off);
-}
-
-/* melpe_dec.c:33-49, the parse of one frame per channel: channel c's frame
- * starts at stream[pos[c]] and its stream ends at end[c].  pos_next may be
- * pos itself (a lane touches only its own slot), hence no restrict. */
-__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_parse(const unsigned char *stream, const uint32_t *pos,
-							       const uint32_t *end, uint32_t *pos_next,
-							       unsigned char *bits, uint8_t *voiced, uint8_t *lens,
-							       const uint8_t *active, int channels)
-{
-	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
-	if (c >= channels)
-		return;
-	const uint32_t p = pos[c];
-	unsigned len = 0;
-	if ((!active || active[c]) && p < end[c]) {
-		const unsigned char *f = stream + p;
-		unsigned char *b = bits + c * SFMT_BYTES;
-		len = sfmt_rx_len(f[0], end[c] - p);
-		if (len == 1) {
-#pragma unroll
-			for (int j = 0; j < SFMT_BYTES; j++)
-				b[j] = 0;
-		} else if (len == SFMT_BYTES) {
-			sfmt_unswap(f, b);
-		}
-	}
-	lens[c] = (uint8_t) len;
-	voiced[c] = len == SFMT_BYTES;
-	if (pos_next)
-		pos_next[c] = p + (len == SFMT_TRUNCATED ? 0u : len);
-}
-
-/* melpe_dec.c:37: 540 zero samples for the channels the parse found silent,
- * one wave per channel, 8 bytes per lane and store */
-static_assert(MELPE_SF_SAMPLES * sizeof(int16_t) % sizeof(uint2) == 0, "a channel's PCM row in 8-byte words");
-__global__ __launch_bounds__(STREAM_BLOCK) void k_stream_zero(uint2 *sp, const uint8_t *lens, int channels)
-{
-	const int words = (int) (MELPE_SF_SAMPLES * sizeof(int16_t) / sizeof(uint2));
-	const long c = blockIdx.x * (long) (STREAM_BLOCK / WAVE) + threadIdx.x / WAVE;
-	if (c >= channels || lens[c] != 1)
-		return;
-	uint2 *row = sp + c * words;
-	for (int i = threadIdx.x & (WAVE - 1); i < words; i += WAVE)
-		row[i] = make_uint2(0u, 0u);
-}
-
-/* Modulate (modem.h, modem/modem.c:136): one wave per (channel, packet).
- * The packet's starting state follows from the channel's state at launch:
- * the previous bit is the last bit of the previous packet (its parity bit
- * 89) and the muting flag alternates per packet.  Lane pairs of samples are
- * stored as dwords: coalesced 6,480-byte rows per packet. */
-__global__ __launch_bounds__(256) void k_modulate(ModemState *st, const uint8_t *pkts, int16_t *pcm,
-						  int channels, int packets, const uint8_t *active)
-{
-	long w = blockIdx.x * 4L + threadIdx.x / WAVE;
-	int lane = threadIdx.x % WAVE;
-	if (w >= (long) channels * packets)
-		return;
-	int c = (int) (w / packets), k = (int) (w - (long) c * packets);
-	if (active && !active[c])
-		return;
-	const uint8_t *d = pkts + w * 11;
-	int prev0 = k ? modem_tx_bit(d - 11, MODEM_BITS - 1) : st[c].lastb;
-	int vad = st[c].vadtr ^ (k & 1);
-	uint32_t *o = (uint32_t *) (pcm + w * MODEM_PKT_SAMPLES);
-	for (int q = lane; q < MODEM_PKT_SAMPLES / 2; q += WAVE) {
-		int s0 = 2 * q, t = s0 / 36, ii = s0 - 36 * t;
-		int b = modem_tx_bit(d, t);
-		int prev = t ? modem_tx_bit(d, t - 1) : prev0;
-		uint32_t lo = (uint16_t) modem_sample(b, prev, vad, ii);
-		uint32_t hi = (uint16_t) modem_sample(b, prev, vad, ii + 1);
-		o[q] = lo | (hi << 16);
-	}
-}
-
-/* the state update of a whole modulate launch, after k_modulate has read it */
-__global__ __launch_bounds__(WAVE) void k_modulate_state(ModemState *st, const uint8_t *pkts,
-							 int channels, int packets, const uint8_t *active)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= channels || (active && !active[c]))
-		return;
-	st[c].lastb = modem_tx_bit(pkts + ((long) c * packets + packets - 1) * 11, MODEM_BITS - 1);
-	st[c].vadtr ^= packets & 1;
-}
-
-/* Demodulate (modem.h, modem/modem.c:186): one lane per channel, `calls`
- * successive calls as rx.c:294-297 makes them (pos advances by the return
- * value, data persists); a call that would read past the channel's stride
- * returns -1 and stops the channel.
- *
- * Each lane reads its own row, so a direct read of the stream is a 2-byte
- * load whose 64 lanes touch 64 different rows -- ~1,900 of them per call.
- * Instead the samples of up to DEMOD_CALLS calls are staged once into the
- * lane's private segment with 16-byte loads, and the calls read them from
- * there, where the hardware interleaves the 64 lanes' copies per dword: the
- * same-index reads of a wave are one contiguous 256-byte access. */
-#define DEMOD_CALLS 15	/* calls per staged window (one packet time) */
-#define DEMOD_ADV_MAX (MODEM_BLOCK_SAMPLES + 8)	/* a call's largest return (q <= 8) */
-#define DEMOD_WIN (((DEMOD_CALLS - 1) * DEMOD_ADV_MAX + MODEM_LOOKAHEAD + 8 + 7) & ~7)
-
-struct DemodLane {
-	uint8_t guard[FLAT_GUARD_BYTES];
-	ModemState S;
-	alignas(16) int16_t w[DEMOD_WIN];
-};
-
-/* w[sh + i] = src[i], i < n, where sh = the samples before src in its
- * 16-byte line: whole lines by dwordx4 (each starts at or after the line
- * that holds src[0], and ends at or before src[n]), the last partial line
- * sample by sample, so nothing past src[n - 1] is read */
-__device__ __forceinline__ int demod_stage(int16_t *w, const int16_t *src, int n)
-{
-	const int sh = (int) (((uintptr_t) src & 15) >> 1);
-	/* pointer arithmetic on src (not an integer cast) keeps the global
-	 * address space, so these are global_ loads, not FLAT */
-	const v4u32 *g = (const v4u32 *) (src - sh);
-	v4u32 *d = (v4u32 *) w;
-	const int full = (sh + n) >> 3;
-	int k = 0;
-	for (; k + 8 <= full; k += 8) {	/* eight loads in flight, then the stores */
-		v4u32 t[8];
-#pragma unroll
-		for (int j = 0; j < 8; j++)
-			t[j] = g[k + j];
-#pragma unroll
-		for (int j = 0; j < 8; j++)
-			d[k + j] = t[j];
-	}
-	for (; k < full; k++)
-		d[k] = g[k];
-	for (int i = full * 8 - sh; i < n; i++)
-		w[sh + i] = src[i];
-	return sh;
-}
-
-/* `calls` successive calls of one lane on its staged window, from sample
- * offset p of its row x; after(k, r) runs after call k with its return value
- * (-1: the call would have read past the row, and the lane stops).  Returns
- * the offset after the last call. */
-template <class F>
-__device__ __forceinline__ int32_t demod_calls(DemodLane &L, const int16_t *x, long stride, int32_t p,
-						uint8_t *d, int calls, F &&after)
-{
-	int32_t r = 0;
-	for (int k0 = 0; k0 < calls && r >= 0; k0 += DEMOD_CALLS) {
-		const int nk = calls - k0 < DEMOD_CALLS ? calls - k0 : DEMOD_CALLS;
-		/* the window: from p, the lookahead of the chunk's last call at
-		 * the largest advance per call, never past the row */
-		long base = 0;
-		if (p >= 0 && p + MODEM_LOOKAHEAD <= stride) {
-			long end = (long) p + (long) (nk - 1) * DEMOD_ADV_MAX + MODEM_LOOKAHEAD;
-			if (end > stride)
-				end = stride;
-			base = p - demod_stage(L.w, x + p, (int) (end - p));
-		}
-		for (int k = k0; k < k0 + nk; k++) {
-			r = -1;
-			if (p >= 0 && p + MODEM_LOOKAHEAD <= stride) {
-				r = modem_demod(&L.S, L.w + (p - base), d);
-				p += r;
-			}
-			after(k, r);
-			if (r < 0)
-				break;
-		}
-	}
-	return p;
-}
-
-__global__ __launch_bounds__(WAVE) void k_demodulate(ModemState *st, const int16_t *pcm, long stride,
-						     int32_t *pos, uint8_t *data, uint8_t *out,
-						     int32_t *ret, int channels, int calls,
-						     const uint8_t *active)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= channels || (active && !active[c]))
-		return;
-	DemodLane L;
-	PIN_FRAME(L);
-	L.S = st[c];
-	uint8_t d[12];
-	for (int i = 0; i < 12; i++)
-		d[i] = data[12L * c + i];
-	const int32_t p = demod_calls(L, pcm + (long) c * stride, stride, pos[c], d, calls, [&](int k, int32_t r) {
-		if (out)
-			for (int i = 0; i < 12; i++)
-				out[((long) c * calls + k) * 12 + i] = d[i];
-		if (ret)
-			ret[(long) c * calls + k] = r;
-	});
-	st[c] = L.S;
-	pos[c] = p;
-	for (int i = 0; i < 12; i++)
-		data[12L * c + i] = d[i];
-}
-
-/*
- * The receive loop (rx.c:294-361, rxline.h): k_demodulate's lane and window,
- * with the ready-block step run inside the call loop on the lane's buf --
- * the fber update, ProcessCtr on the channel's link record (loaded at the
- * event and stored after it: its 32 soft bits would otherwise sit in the
- * lane's registers through every Demodulate call), the fau update -- and the
- * block handed out into the channel's next slot.  Lanes of a wave reach their
- * events at different calls, so the wave may run the branch in every
- * iteration; no lane waits on another, and every loop is bounded by `calls`
- * or a constant.
- *
- * Outputs are slot-major (slot j = rows j * channels ...).  A lane writes the
- * bytes of its own rows only: an 11-byte bits row as the bytes up to its
- * first dword boundary, whole dwords, and the bytes after the last; the
- * 8-byte info row as two dwords; nothing at or past `slots`.
- */
-typedef uint32_t rxl_u32a __attribute__((__may_alias__));
-
-__device__ __forceinline__ void rxl_store_bits(uint8_t *row, const uint8_t *d)
-{
-	const int head = (int) ((4 - ((uintptr_t) row & 3)) & 3);
-	int i = 0;
-	for (; i < head; i++)
-		row[i] = d[i];
-	for (; i + 4 <= VC_PKT_BYTES; i += 4)
-		*(rxl_u32a *) (row + i) = (uint32_t) d[i] | ((uint32_t) d[i + 1] << 8) |
-					  ((uint32_t) d[i + 2] << 16) | ((uint32_t) d[i + 3] << 24);
-	for (; i < VC_PKT_BYTES; i++)
-		row[i] = d[i];
-}
-
-__global__ __launch_bounds__(WAVE) void k_rx_line(ModemState *st, LinkState *lk, RxLineState *rx,
-						  const int16_t *pcm, long stride, int32_t *pos, uint8_t *data,
-						  uint8_t *bits, uint8_t *voice, uint32_t *info, uint8_t *count,
-						  int channels, int calls, int slots, const uint8_t *active)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= channels || (active && !active[c]))
-		return;
-	DemodLane L;
-	PIN_FRAME(L);
-	L.S = st[c];
-	uint8_t d[12];
-	for (int i = 0; i < 12; i++)
-		d[i] = data[12L * c + i];
-	float fber = rx[c].fber, fau = rx[c].fau;
-	uint32_t blocks = rx[c].blocks;
-	int n = 0;	/* blocks handed out by this launch */
-	const int32_t p = demod_calls(L, pcm + (long) c * stride, stride, pos[c], d, calls, [&](int k, int32_t r) {
-		if (r < 0 || !(d[11] & 0x80))
-			return;
-		const RxLineEvent ev = rxline_block(d, &lk[c], &fber, &fau);
-		blocks++;
-		if (n < slots) {
-			const long row = (long) n * channels + c;
-			rxl_store_bits(bits + row * VC_PKT_BYTES, d);
-			voice[row] = ev.kind == RXL_KIND_VOICE;
-			uint32_t w0, w1;
-			rxline_info(&ev, k, &w0, &w1);
-			info[2 * row] = w0;
-			info[2 * row + 1] = w1;
-			n++;
-		}
-		d[11] = 0;	/* rx.c:361: the block is taken, the output slot being free */
-	});
-	st[c] = L.S;
-	pos[c] = p;
-	for (int i = 0; i < 12; i++)
-		data[12L * c + i] = d[i];
-	rx[c].fber = fber;
-	rx[c].fau = fau;
-	rx[c].blocks = blocks;
-	count[c] = (uint8_t) n;
-}
-
-/* after k_rx_line: 540 zero samples for every slot that holds a block which
- * is not voice (rx.c:360), one wave per (slot, channel) */
-__global__ __launch_bounds__(STREAM_BLOCK) void k_rx_line_zero(uint2 *sp, const uint8_t *voice,
-								 const uint8_t *count, const uint8_t *active,
-								 int channels, int slots)
-{
-	const int words = (int) (MELPE_SF_SAMPLES * sizeof(int16_t) / sizeof(uint2));
-	const long w = blockIdx.x * (long) (STREAM_BLOCK / WAVE) + threadIdx.x / WAVE;
-	if (w >= (long) slots * channels)
-		return;
-	const int j = (int) (w / channels), c = (int) (w - (long) j * channels);
-	if ((active && !active[c]) || j >= count[c] || voice[w])
-		return;
-	uint2 *row = sp + w * words;
-	for (int i = threadIdx.x & (WAVE - 1); i < words; i += WAVE)
-		row[i] = make_uint2(0u, 0u);
-}
-
-/* the decoder's mask of slot j: the channels whose block j is voice */
-__global__ __launch_bounds__(STREAM_BLOCK) void k_rx_line_mask(uint8_t *mask, const uint8_t *voice,
-								 const uint8_t *count, const uint8_t *active,
-								 int channels, int j)
-{
-	const long c = blockIdx.x * (long) STREAM_BLOCK + threadIdx.x;
-	if (c >= channels)
-		return;
-	mask[c] = (!active || active[c]) && j < count[c] && voice[(long) j * channels + c];
-}
-
-__global__ __launch_bounds__(WAVE) void k_modem_reset(ModemState *st, const uint8_t *mask, int channels)
-{
-	int c = blockIdx.x * WAVE + threadIdx.x;
-	if (c >= channels || (mask && !mask[c]))
-		return;
-	ModemState z;
-	modem_reset(&z);
-	st[c] = z;
-}
-
-/* device basic-op parity test: out[i] = op(a[i], b[i], c[i]) with the
- * device build of ops.h (ops_eval.h) */
-__global__ __launch_bounds__(256) void k_ops_eval(int op, const int64_t *A, const int32_t *B,
-						  const int32_t *C, int64_t *out, long n)
-{
-	long i = blockIdx.x * (long) blockDim.x + threadIdx.x;
-	if (i >= n)
-		return;
-	int64_t a = A[i];
-	int32_t b = B ? B[i] : 0, c = C ? C[i] : 0;
-	int64_t r = 0;
-	switch (op) {
-#define OPS_CASE(id, name, call) case id: r = (int64_t) (call); break;
-	MELPE_OPS_EVAL_LIST(OPS_CASE)
-#undef OPS_CASE
-	default: r = 0;
-	}
-	out[i] = r;
-}
-
-/* divide_s over its whole domain, 0 <= num <= den < 2^15 (den >= 1): one
- * thread per denominator sums q(num) * (num * 0x9E3779B97F4A7C15 + 1) over
- * every numerator in uint64 arithmetic -- a digest that any wrong quotient
- * changes (tests/test_device_ops.py forms the same sums from the
- * reference's divide_s) */
-__global__ __launch_bounds__(256) void k_divide_s_sweep(uint64_t *digest)
-{
-	const int den = blockIdx.x * blockDim.x + threadIdx.x + 1;
-	if (den > 32767)
-		return;
-	uint64_t h = 0;
-	for (int num = 0; num <= den; num++)
-		h += (uint64_t) (uint16_t) divide_s((Word16) num, (Word16) den) *
-		     ((uint64_t) num * 0x9E3779B97F4A7C15ull + 1u);
-	digest[den - 1] = h;
-}
-
-/* device helper self-test (helpers_eval.h): lane i copies its HE_N
- * samples into a private array -- the codec's streams read the private
- * segment, at per-lane alignments -- and runs helper `mode` on it with
- * (a, b, len) = args[4i .. 4i+2], HE_OUT int32 results per lane */
-__global__ __launch_bounds__(WAVE) void k_helpers_eval(int mode, const int16_t *src, const int32_t *args,
-						       int32_t *out, int n)
-{
-	int i = blockIdx.x * WAVE + threadIdx.x;
-	if (i >= n)
-		return;
-	struct {
-		uint8_t guard[FLAT_GUARD_BYTES];
-		int16_t buf[HE_N];
-		int32_t o[HE_OUT];
-	} L;
-	PIN_FRAME(L);
-	for (int k = 0; k < HE_N; k++)
-		L.buf[k] = src[(size_t) i * HE_N + k];
-	for (int k = 0; k < HE_OUT; k++)
-		L.o[k] = 0;
-	he_eval(mode, L.buf, args[4 * i], args[4 * i + 1], args[4 * i + 2], L.o);
-	for (int k = 0; k < HE_OUT; k++)
-		out[(size_t) i * HE_OUT + k] = L.o[k];
-}
-
-/* ------------------------------------------------------------------ */
-/* host side                                                          */
-/* ------------------------------------------------------------------ */
 
 static thread_local std::string g_err;
 
@@ -728,43 +126,9 @@ static int stage_get(int dev, size_t bytes, void **out)
 	return 0;
 }
 
-/*
- * Lane order by pitch class (MELPE_BIN, default on).
- *
- * k_enc_ana and k_decode run one channel per lane, and their loops follow
- * each channel's own pitch period and voicing: a synthesis period costs
- * O(L^2) in realIDFT and a frame holds 180/L of them, the analysis windows
- * and harmonic counts follow the pitch, and unvoiced frames take other
- * branches.  A wave pays the slowest of its 64 channels in every such loop.
- * So before each launch the live channels are counting-sorted into 568
- * classes -- voiced frames of the channel's last superframe (0..3) x its last
- * pitch in 1-sample steps -- and lane g of the kernel runs channel perm[g];
- * lanes at or past the live count exit at once, so a ragged mask also packs
- * the live channels into the fewest waves.  Each channel's arithmetic is
- * untouched (the order only decides which channels share a wave), so the
- * output is the same bit for bit; the order within a class follows the
- * atomics and is not reproducible, which nothing depends on.
- */
-#define BIN_PITCHES 142	/* pitch classes: 20 .. 161 samples in 1-sample steps */
-#define NBIN 640	/* room for the 4 x BIN_PITCHES = 568 classes (progprio.h and AnaGate index past it) */
-static_assert(4 * BIN_PITCHES <= NBIN, "every class has a counter");
-#define NOT_LIVE 0xffff	/* the key of a channel that is not live */
-static_assert(NBIN < NOT_LIVE, "class ids and the not-live mark must fit the uint16 keys");
-struct BinBuf {
-	int *perm = nullptr;	/* [C] lane -> channel */
-	uint16_t *key = nullptr;	/* [C] class of each channel (NOT_LIVE: not live) */
-	/* [0, NBIN) counts, [NBIN, 2 NBIN) next slot of each class, [2 NBIN]
-	 * the live count, [2 NBIN + 1] the mapping the last analysis launch ran
-	 * (AnaGate tag: 1 lane, 4 four-wave; 0 none yet), [2 NBIN + 2] the
-	 * launch's progress counter (k_ana.hip ana_ckpt) */
-	unsigned *ctl = nullptr;
-	/* The buffers are one per engine and direction, but *_dev calls may
-	 * come on different streams: the sort of a call waits for the kernel
-	 * that read the previous call's order (its stream recorded `done`). */
-	hipEvent_t done = nullptr;
-	hipStream_t last = nullptr;
-	bool used = false;
-};
+/* The lane order (MELPE_BIN, default on): k_state.hip has the sort and what
+ * its classes are, launch.h the buffers of one order (BinBuf); here, their
+ * host bookkeeping. */
 
 /* what a kernel is launched with: b's order and live count when the order is
  * used, nulls (identity lanes + mask) when it is not */
@@ -793,109 +157,6 @@ static hipError_t bin_alloc(BinBuf *b, int channels)
 	b->ctl = (unsigned *) (p + pb);
 	b->key = (uint16_t *) (p + pb + cb);
 	return hipMemset(b->ctl, 0, cb);
-}
-
-/* the class of one record, from its last superframe: the voiced frames
- * (quant_par uv_flag, 0 = voiced) and the pitch (Q7) of its last frame, in
- * 1-sample steps.  Coarser steps (2, 3, 5 samples) and the mean pitch lost
- * to this key in round 5 on MI355X at 262,144 channels, two runs each
- * (profiles/r05_s_keys.txt): k_decode 8.52 -> 8.39 ms and the analysis
- * 31.11 -> 31.01 ms from the 3-sample key to this one. */
-__device__ __forceinline__ int bin_class(const char *rec, int off_par, int off_uv)
-{
-	const int16_t *uv = (const int16_t *) (rec + off_uv);
-	const int nv = (uv[0] == 0) + (uv[1] == 0) + (uv[2] == 0);
-	int b = (*(const int16_t *) (rec + off_par + (NF - 1) * sizeof(MelpParam)) >> 7) - 20;
-	b = b < 0 ? 0 : (b > BIN_PITCHES - 1 ? BIN_PITCHES - 1 : b);
-	return nv * BIN_PITCHES + b;
-}
-
-/* The second lane order of the encoder (ana_launch): the class of a record
- * is the voicing pattern of the superframe being encoded, the uv_flags of
- * par[0..2] as k_enc_ana's sc_ana left them (quant.h lsf_uvc: frame 0 in bit
- * 2), 8 classes.  lsf_vq, quant_fsmag and the residual loop branch on it. */
-#define KEY_PITCH 0	/* bin_class */
-#define KEY_VOICING 1	/* bin_class_uvc */
-__device__ __forceinline__ int bin_class_uvc(const char *rec, int off_par)
-{
-	const MelpParam *par = (const MelpParam *) (rec + off_par);
-	return (par[0].uv_flag ? 4 : 0) | (par[1].uv_flag ? 2 : 0) | (par[2].uv_flag ? 1 : 0);
-}
-
-/* The lane order of the synthesis from parameter rows (dec_launch): there
- * the superframe being synthesised is known before the launch, so the class
- * is cut by it, not by the previous one as bin_class must for k_decode -- the
- * voiced frames among the rows' uv_flags and the pitch the last frame will be
- * synthesised with (an unvoiced frame runs at UV_PITCH_Q7, decoder.h
- * syn_par_head), in 1-sample steps.  The rows are read as the caller left
- * them, before admission: any value lands in a class. */
-#define KEY_ROWS 2	/* bin_class_rows */
-__device__ __forceinline__ int bin_class_rows(const char *row)
-{
-	const MelpParam *par = (const MelpParam *) row;
-	const int nv = (par[0].uv_flag == 0) + (par[1].uv_flag == 0) + (par[2].uv_flag == 0);
-	int b = ((par[NF - 1].uv_flag ? UV_PITCH_Q7 : par[NF - 1].pitch) >> 7) - 20;
-	b = b < 0 ? 0 : (b > BIN_PITCHES - 1 ? BIN_PITCHES - 1 : b);
-	return nv * BIN_PITCHES + b;
-}
-
-template <int KEY>
-__global__ __launch_bounds__(256) void k_bin_count(const char *rec, size_t stride, int off_par,
-						   int off_uv, const uint8_t *active, int n, BinBuf b)
-{
-	__shared__ unsigned cnt[NBIN];
-	for (int k = threadIdx.x; k < NBIN; k += blockDim.x)
-		cnt[k] = 0;
-	__syncthreads();
-	int c = blockIdx.x * blockDim.x + threadIdx.x;
-	if (c < n) {
-		int k = NOT_LIVE;
-		if (!active || active[c]) {
-			k = KEY == KEY_VOICING ? bin_class_uvc(rec + (size_t) c * stride, off_par)
-			    : KEY == KEY_ROWS  ? bin_class_rows(rec + (size_t) c * stride + off_par)
-					       : bin_class(rec + (size_t) c * stride, off_par, off_uv);
-			atomicAdd(&cnt[k], 1u);
-		}
-		b.key[c] = (uint16_t) k;
-	}
-	__syncthreads();
-	for (int k = threadIdx.x; k < NBIN; k += blockDim.x)
-		if (cnt[k])
-			atomicAdd(&b.ctl[k], cnt[k]);
-}
-
-__global__ void k_bin_scan(BinBuf b)
-{
-	if (threadIdx.x == 0) {
-		unsigned acc = 0;
-		for (int k = 0; k < NBIN; k++) {
-			b.ctl[NBIN + k] = acc;
-			acc += b.ctl[k];
-		}
-		b.ctl[2 * NBIN] = acc;
-		b.ctl[2 * NBIN + 1] = 0;	/* the mapping tag: the launch that runs sets it */
-		b.ctl[2 * NBIN + 2] = 0;	/* the lane kernels' progress counter (k_ana.hip ana_ckpt) */
-	}
-}
-
-__global__ __launch_bounds__(256) void k_bin_scatter(int n, BinBuf b)
-{
-	__shared__ unsigned cnt[NBIN], base[NBIN];
-	for (int k = threadIdx.x; k < NBIN; k += blockDim.x)
-		cnt[k] = 0;
-	__syncthreads();
-	int c = blockIdx.x * blockDim.x + threadIdx.x;
-	int k = c < n ? b.key[c] : NOT_LIVE;
-	unsigned r = 0;
-	if (k != NOT_LIVE)
-		r = atomicAdd(&cnt[k], 1u);
-	__syncthreads();
-	for (int j = threadIdx.x; j < NBIN; j += blockDim.x)
-		if (cnt[j])
-			base[j] = atomicAdd(&b.ctl[NBIN + j], cnt[j]);
-	__syncthreads();
-	if (k != NOT_LIVE)
-		b.perm[base[k] + r] = c;
 }
 
 static bool bin_enabled(void)
@@ -931,20 +192,7 @@ static hipError_t bin_launch(int order, BinBuf &b, const void *rec, size_t strid
 	hipError_t er;
 	if (!prepared && (er = bin_prepare(b, s)) != hipSuccess)
 		return er;
-	unsigned g = (unsigned) ((n + 255) / 256);
-	if (key == KEY_VOICING)
-		k_bin_count<KEY_VOICING><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
-	else if (key == KEY_ROWS)
-		k_bin_count<KEY_ROWS><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
-	else
-		k_bin_count<KEY_PITCH><<<g, 256, 0, s>>>((const char *) rec, stride, off_par, off_uv, active, n, b);
-	if ((er = hipGetLastError()) != hipSuccess)
-		return er;
-	k_bin_scan<<<1, WAVE, 0, s>>>(b);
-	if ((er = hipGetLastError()) != hipSuccess)
-		return er;
-	k_bin_scatter<<<g, 256, 0, s>>>(n, b);
-	return hipGetLastError();
+	return (hipError_t) kl_bin_sort(key, (const char *) rec, stride, off_par, off_uv, active, n, b, s);
 }
 
 /* after the kernel that reads b's order, on the same stream */
@@ -1422,9 +670,9 @@ static int state_aligned(const char *who, const void *d_state)
 static int vad_launch(void *d_state, const void *d_sp, void *d_votes, void *d_gate, const void *d_active,
 		      int channels, hipStream_t s)
 {
-	k_vad<<<grid_for(channels), WAVE, 0, s>>>((VadState *) d_state, (const int16_t *) d_sp, (uint8_t *) d_votes,
-						  (uint8_t *) d_gate, (const uint8_t *) d_active, channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_vad((VadState *) d_state, (const int16_t *) d_sp, (uint8_t *) d_votes, (uint8_t *) d_gate,
+			    (const uint8_t *) d_active, channels, s))
+		return fail("vad_launch", (hipError_t) rc);
 	return 0;
 }
 
@@ -1629,8 +877,8 @@ static int engine_reserve(melpe_engine *e)
 		size_t dec_lane = kl_dec_private(1, 0) > kl_parse_private() ? kl_dec_private(1, 0) : kl_parse_private();
 		/* (nor does the receive loop's, the demodulator's window plus a
 		 * link record: melpe_rx_line_private_bytes) */
-		if ((size_t) melpe_rx_line_private_bytes() > dec_lane)
-			dec_lane = (size_t) melpe_rx_line_private_bytes();
+		if (kl_rx_line_private() > dec_lane)
+			dec_lane = kl_rx_line_private();
 		/* the synthesis from rows: the decoder's frame without the channel
 		 * read's (engine_warm warms it only if it is the larger) */
 		if (kl_dec_private(1, 1) > dec_lane)
@@ -1876,9 +1124,8 @@ int melpe_engine_reset_dev(melpe_engine *e, const void *d_mask, int which, void 
 	if (!e || which < 1 || which > 3)
 		return fail_msg("melpe_engine_reset_dev: bad arguments");
 	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
-		k_reset<<<grid_for(e->channels), WAVE, 0, s>>>(
-			e->d_enc, e->d_dec, (const uint8_t *) d_mask, e->channels, which);
-		HIPCHK(hipGetLastError());
+		if (int rc = kl_reset(e->d_enc, e->d_dec, (const uint8_t *) d_mask, e->channels, which, s))
+			return fail("melpe_engine_reset_dev", (hipError_t) rc);
 		return 0;
 	});
 }
@@ -1896,9 +1143,8 @@ int melpe_engine_reset(melpe_engine *e, const uint8_t *mask_host, int which)
 	const uint8_t *m = stage_mask(e, mask_host, &rc);
 	if (rc)
 		return rc;
-	k_reset<<<grid_for(e->channels), WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, m,
-								  e->channels, which);
-	HIPCHK(hipGetLastError());
+	if ((rc = kl_reset(e->d_enc, e->d_dec, m, e->channels, which, e->stream)))
+		return fail("melpe_engine_reset", (hipError_t) rc);
 	HOST_FINISH(e);
 	return 0;
 }
@@ -2381,9 +1627,8 @@ int melpe_synth_seed(melpe_engine *e, uint32_t run_seed, uint32_t first_channel)
 		return fail_msg("null engine");
 	DEVGUARD(e->device);
 	HOST_LOCK(e);
-	k_synth_seed<<<grid_for(e->channels), WAVE, 0, e->stream>>>(e->d_syn, run_seed,
-								      first_channel, e->channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_synth_seed(e->d_syn, run_seed, first_channel, e->channels, e->stream))
+		return fail("melpe_synth_seed", (hipError_t) rc);
 	HOST_FINISH(e);
 	return 0;
 }
@@ -2393,8 +1638,8 @@ int melpe_synth_dev(melpe_engine *e, void *d_sp, int samples, void *hip_stream)
 	if (!e || !d_sp || samples <= 0)
 		return fail_msg("melpe_synth_dev: bad arguments");
 	return engine_call(e, (hipStream_t) hip_stream, TIME_NONE, [&](hipStream_t s) {
-		k_synth<<<grid_for(e->channels), WAVE, 0, s>>>(e->d_syn, (int16_t *) d_sp, samples, e->channels);
-		HIPCHK(hipGetLastError());
+		if (int rc = kl_synth(e->d_syn, (int16_t *) d_sp, samples, e->channels, s))
+			return fail("melpe_synth_dev", (hipError_t) rc);
 		return 0;
 	});
 }
@@ -2505,8 +1750,7 @@ static void single_init(const char *who, bool rate2400)
 {
 	melpe_engine *e = single_engine();
 	DevGuard dg(e->device);
-	k_melpe_i<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec);
-	if (hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess) {
+	if (kl_melpe_i(e->d_enc, e->d_dec, e->stream) || hipStreamSynchronize(e->stream) != hipSuccess) {
 		fprintf(stderr, "libmelpe_amd: %s failed\n", who);
 		abort();
 	}
@@ -2560,12 +1804,10 @@ void melpe_s(short *sp, unsigned char *buf)
 	DevGuard dg(e->device);
 	/* after melpe_i2, synthesis() at RATE2400: 7 bytes -> 180 samples */
 	const bool r24 = g_single_rate2400;
-	k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 0);
-	int rc = hipGetLastError() != hipSuccess ||
+	int rc = kl_share_params(e->d_enc, e->d_dec, 0, e->stream) ||
 		 (r24 ? melpe_decode2400_host(e, sp, buf, nullptr) : melpe_decode_host(e, sp, buf, nullptr));
 	if (!rc) {
-		k_share_params<<<1, WAVE, 0, e->stream>>>(e->d_enc, e->d_dec, 1);
-		rc = hipGetLastError() != hipSuccess || hipStreamSynchronize(e->stream) != hipSuccess;
+		rc = kl_share_params(e->d_enc, e->d_dec, 1, e->stream) || hipStreamSynchronize(e->stream) != hipSuccess;
 	}
 	if (rc) {
 		fprintf(stderr, "libmelpe_amd: melpe_s%s failed: %s\n", r24 ? " (2400)" : "", g_err.c_str());
@@ -2590,9 +1832,8 @@ int melpe_modem_reset_dev(void *d_state, int channels, const void *d_mask, void 
 {
 	if (int r = modem_state_ok(d_state, channels))
 		return r;
-	k_modem_reset<<<grid_for(channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(ModemState *) d_state, (const uint8_t *) d_mask, channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_modem_reset((ModemState *) d_state, (const uint8_t *) d_mask, channels, (hipStream_t) hip_stream))
+		return fail("melpe_modem_reset_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2616,15 +1857,9 @@ int melpe_modulate_dev(void *d_state, const void *d_pkts, void *d_pcm, int chann
 	long waves = (long) channels * packets;
 	if ((waves + 3) / 4 > 0x7fffffffL)
 		return fail_msg("melpe_modulate_dev: too many packets");
-	hipStream_t s = (hipStream_t) hip_stream;
-	k_modulate<<<(unsigned) ((waves + 3) / 4), 256, 0, s>>>(
-		(ModemState *) d_state, (const uint8_t *) d_pkts, (int16_t *) d_pcm, channels, packets,
-		(const uint8_t *) d_active);
-	HIPCHK(hipGetLastError());
-	k_modulate_state<<<grid_for(channels), WAVE, 0, s>>>(
-		(ModemState *) d_state, (const uint8_t *) d_pkts, channels, packets,
-		(const uint8_t *) d_active);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_modulate((ModemState *) d_state, (const uint8_t *) d_pkts, (int16_t *) d_pcm, channels, packets,
+				 (const uint8_t *) d_active, (hipStream_t) hip_stream))
+		return fail("melpe_modulate_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2637,11 +1872,10 @@ int melpe_demodulate_dev(void *d_state, const void *d_pcm, long stride, void *d_
 	if (!d_pcm || !d_pos || !d_data || calls <= 0 || stride < MODEM_LOOKAHEAD ||
 	    ((uintptr_t) d_pos & 3) || ((uintptr_t) d_ret & 3))
 		return fail_msg("melpe_demodulate_dev: bad arguments");
-	k_demodulate<<<grid_for(channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(ModemState *) d_state, (const int16_t *) d_pcm, stride, (int32_t *) d_pos,
-		(uint8_t *) d_data, (uint8_t *) d_out, (int32_t *) d_ret, channels, calls,
-		(const uint8_t *) d_active);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_demodulate((ModemState *) d_state, (const int16_t *) d_pcm, stride, (int32_t *) d_pos,
+				   (uint8_t *) d_data, (uint8_t *) d_out, (int32_t *) d_ret, channels, calls,
+				   (const uint8_t *) d_active, (hipStream_t) hip_stream))
+		return fail("melpe_demodulate_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2651,10 +1885,9 @@ int melpe_ops_eval_dev(int op, const void *d_a, const void *d_b, const void *d_c
 	if (op < 0 || op >= MELPE_OPS_EVAL_COUNT || !d_a || !d_out || n <= 0 ||
 	    (n + 255) / 256 > 0x7fffffffL)
 		return fail_msg("melpe_ops_eval_dev: bad arguments");
-	k_ops_eval<<<(unsigned) ((n + 255) / 256), 256, 0, (hipStream_t) hip_stream>>>(
-		op, (const int64_t *) d_a, (const int32_t *) d_b, (const int32_t *) d_c,
-		(int64_t *) d_out, n);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_ops_eval(op, (const int64_t *) d_a, (const int32_t *) d_b, (const int32_t *) d_c,
+				 (int64_t *) d_out, n, (hipStream_t) hip_stream))
+		return fail("melpe_ops_eval_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2662,8 +1895,8 @@ int melpe_divide_s_sweep_dev(void *d_digest, void *hip_stream)
 {
 	if (!d_digest)
 		return fail_msg("melpe_divide_s_sweep_dev: null argument");
-	k_divide_s_sweep<<<(32767 + 255) / 256, 256, 0, (hipStream_t) hip_stream>>>((uint64_t *) d_digest);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_divide_s_sweep((uint64_t *) d_digest, (hipStream_t) hip_stream))
+		return fail("melpe_divide_s_sweep_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2674,9 +1907,9 @@ int melpe_helpers_eval_dev(int mode, const void *d_src, const void *d_args, void
 		return fail_msg("melpe_helpers_eval_dev: bad arguments");
 	if (n == 0)
 		return 0;
-	k_helpers_eval<<<grid_for(n), WAVE, 0, (hipStream_t) hip_stream>>>(
-		mode, (const int16_t *) d_src, (const int32_t *) d_args, (int32_t *) d_out, n);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_helpers_eval(mode, (const int16_t *) d_src, (const int32_t *) d_args, (int32_t *) d_out, n,
+				     (hipStream_t) hip_stream))
+		return fail("melpe_helpers_eval_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2785,10 +2018,9 @@ int melpe_voice_crypt_dev(void *d_pkts, const void *d_counters, const void *d_ke
 	long blocks = (n + 255) / 256;
 	if (blocks > 0x7fffffffL)
 		return fail_msg("melpe_voice_crypt_dev: too many packets");
-	k_voice_crypt<<<(unsigned) blocks, 256, 0, (hipStream_t) hip_stream>>>(
-		(unsigned char *) d_pkts, (const uint32_t *) d_counters, (const uint4 *) d_keys,
-		(const uint8_t *) d_invert, channels, packets, dir);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_voice_crypt((unsigned char *) d_pkts, (const uint32_t *) d_counters, (const uint4 *) d_keys,
+				    (const uint8_t *) d_invert, channels, packets, dir, (hipStream_t) hip_stream))
+		return fail("melpe_voice_crypt_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -2918,9 +2150,8 @@ int melpe_vad_reset_dev(void *d_state, int channels, const void *d_mask, void *h
 		return fail_msg("melpe_vad_reset_dev: bad arguments");
 	if (int rc = state_aligned("melpe_vad_reset_dev", d_state))
 		return rc;
-	k_vad_reset<<<grid_for(channels), WAVE, 0, (hipStream_t) hip_stream>>>(
-		(VadState *) d_state, (const uint8_t *) d_mask, channels);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_vad_reset((VadState *) d_state, (const uint8_t *) d_mask, channels, (hipStream_t) hip_stream))
+		return fail("melpe_vad_reset_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -3043,7 +2274,7 @@ long melpe_stream_pack_work_bytes(int channels)
 {
 	if (channels <= 0)
 		return fail_msg("melpe_stream_pack_work_bytes: bad arguments");
-	return (long) sizeof(uint32_t) * (((long) channels + STREAM_BLOCK - 1) / STREAM_BLOCK);
+	return (long) (sizeof(uint32_t) * kl_stream_pack_work_words(channels));
 }
 
 int melpe_stream_pack_dev(const void *d_bits, const void *d_votes, void *d_last, void *d_out,
@@ -3056,18 +2287,10 @@ int melpe_stream_pack_dev(const void *d_bits, const void *d_votes, void *d_last,
 		return fail_msg("melpe_stream_pack_dev: offs and work must be 4-byte aligned");
 	if ((long) channels * SFMT_BYTES > 0xffffffffL)
 		return fail_msg("melpe_stream_pack_dev: the offsets of so many channels exceed 32 bits");
-	hipStream_t s = (hipStream_t) hip_stream;
-	const unsigned nb = (unsigned) (((long) channels + STREAM_BLOCK - 1) / STREAM_BLOCK);
-	k_stream_len<<<nb, STREAM_BLOCK, 0, s>>>((const uint8_t *) d_votes, (const uint8_t *) d_active,
-						 (uint32_t *) d_work, channels);
-	HIPCHK(hipGetLastError());
-	k_stream_scan<<<1, STREAM_BLOCK, 0, s>>>((uint32_t *) d_work, nb);
-	HIPCHK(hipGetLastError());
-	k_stream_scatter<<<nb, STREAM_BLOCK, 0, s>>>(
-		(const unsigned char *) d_bits, (const uint8_t *) d_votes, (uint8_t *) d_last,
-		(unsigned char *) d_out, (uint32_t *) d_offs, (const uint32_t *) d_work, channels,
-		(const uint8_t *) d_active);
-	HIPCHK(hipGetLastError());
+	if (int rc = kl_stream_pack((const unsigned char *) d_bits, (const uint8_t *) d_votes, (uint8_t *) d_last,
+				    (unsigned char *) d_out, (uint32_t *) d_offs, (uint32_t *) d_work, channels,
+				    (const uint8_t *) d_active, (hipStream_t) hip_stream))
+		return fail("melpe_stream_pack_dev", (hipError_t) rc);
 	return 0;
 }
 
@@ -3086,14 +2309,11 @@ int melpe_rx_stream_dev(melpe_engine *e, const void *d_stream, const void *d_pos
 				"sp 8-byte aligned");
 	const int n = e->channels;
 	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
-		k_stream_parse<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
-			(const unsigned char *) d_stream, (const uint32_t *) d_pos, (const uint32_t *) d_end,
-			(uint32_t *) d_pos_next, (unsigned char *) d_bits, (uint8_t *) d_voiced,
-			(uint8_t *) d_lens, (const uint8_t *) d_active, n);
-		HIPCHK(hipGetLastError());
-		k_stream_zero<<<(unsigned) (((long) n + STREAM_BLOCK / WAVE - 1) / (STREAM_BLOCK / WAVE)),
-				STREAM_BLOCK, 0, s>>>((uint2 *) d_sp, (const uint8_t *) d_lens, n);
-		HIPCHK(hipGetLastError());
+		if (int rc = kl_stream_parse((const unsigned char *) d_stream, (const uint32_t *) d_pos,
+					     (const uint32_t *) d_end, (uint32_t *) d_pos_next, (unsigned char *) d_bits,
+					     (uint8_t *) d_voiced, (uint8_t *) d_lens, (uint2 *) d_sp,
+					     (const uint8_t *) d_active, n, s))
+			return fail("melpe_rx_stream_dev", (hipError_t) rc);
 		HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp, src_bits(d_bits), (const uint8_t *) d_voiced, s));
 		return 0;
 	});
@@ -3107,7 +2327,7 @@ int melpe_rx_line_state_bytes(void)
 
 int melpe_rx_line_private_bytes(void)
 {
-	return (int) private_bytes((const void *) k_rx_line);
+	return (int) kl_rx_line_private();
 }
 
 /* argument errors, refused before any HIP call */
@@ -3146,20 +2366,15 @@ int melpe_rx_line_dev(melpe_engine *e, void *d_modem_state, void *d_link_state, 
 	const uint8_t *act = (const uint8_t *) d_active, *voice = (const uint8_t *) d_voice;
 	const uint8_t *count = (const uint8_t *) d_count;
 	return engine_call(e, (hipStream_t) hip_stream, TIME_LAZY, [&](hipStream_t s) {
-		k_rx_line<<<grid_for(n), WAVE, 0, s>>>(
-			(ModemState *) d_modem_state, (LinkState *) d_link_state, (RxLineState *) d_rx_state,
-			(const int16_t *) d_pcm, stride, (int32_t *) d_pos, (uint8_t *) d_data, (uint8_t *) d_bits,
-			(uint8_t *) d_voice, (uint32_t *) d_info, (uint8_t *) d_count, n, calls, slots, act);
-		HIPCHK(hipGetLastError());
-		const long rows = (long) slots * n, per = STREAM_BLOCK / WAVE;
-		k_rx_line_zero<<<(unsigned) ((rows + per - 1) / per), STREAM_BLOCK, 0, s>>>(
-			(uint2 *) d_sp, voice, count, act, n, slots);
-		HIPCHK(hipGetLastError());
+		if (int rc = kl_rx_line((ModemState *) d_modem_state, (LinkState *) d_link_state,
+					(RxLineState *) d_rx_state, (const int16_t *) d_pcm, stride, (int32_t *) d_pos,
+					(uint8_t *) d_data, (uint2 *) d_sp, (uint8_t *) d_bits, (uint8_t *) d_voice,
+					(uint32_t *) d_info, (uint8_t *) d_count, n, calls, slots, act, s))
+			return fail("melpe_rx_line_dev", (hipError_t) rc);
 		/* slot by slot, as the channel's decoder state carries from block to block */
 		for (int j = 0; j < slots; j++) {
-			k_rx_line_mask<<<(unsigned) (((long) n + STREAM_BLOCK - 1) / STREAM_BLOCK), STREAM_BLOCK, 0, s>>>(
-				e->d_rxmask, voice, count, act, n, j);
-			HIPCHK(hipGetLastError());
+			if (int rc = kl_rx_line_mask(e->d_rxmask, voice, count, act, n, j, s))
+				return fail("melpe_rx_line_dev", (hipError_t) rc);
 			HIPCHK((hipError_t) dec_launch(e, (int16_t *) d_sp + (size_t) j * n * MELPE_SF_SAMPLES,
 						       src_bits((const uint8_t *) d_bits + (size_t) j * n * MELPE_SF_BYTES),
 						       e->d_rxmask, s));

@@ -1,7 +1,7 @@
 /*
  * helpers_eval.h -- the device-only sample-stream and exact-correlator
  * helpers of dsp.h / analysis.h, one selected by `mode`, on a lane's private
- * int16 array, for their self-test (engine.hip k_helpers_eval,
+ * int16 array, for their self-test (k_dsp_eval.hip k_helpers_eval,
  * melpe_helpers_eval_dev; tests/test_device_helpers.py checks the device
  * build and the host build against plain integer arithmetic).
  *

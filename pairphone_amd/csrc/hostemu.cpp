@@ -536,7 +536,7 @@ int emu_enc_params(emu_engine *e, int c, int16_t *out)
 }
 
 /* the single-stream engine's melp_par / quant_par / chbuf hand-over around
- * melpe_s (engine.hip k_share_params), channel 0 */
+ * melpe_s (k_state.hip k_share_params), channel 0 */
 int emu_share(emu_engine *e, int dir)
 {
 	EncAna *E = &e->enc[0].a;

@@ -1,16 +1,20 @@
 /*
- * kern.h -- shared by the translation units that carry the codec: engine.hip,
- * k_npp.hip, k_ana.hip, k_quant.hip, k_ana_mw.hip, k_harm.hip, k_dec.hip, k_r24.hip,
- * k_dsp_eval.hip, k_ana_eval.hip and k_par.hip (k_link.hip has no codec tables and includes
- * only launch.h).
+ * kern.h -- shared by engine.hip (host code only) and the kernel translation
+ * units that use the codec's types and lane conventions: k_npp.hip,
+ * k_ana.hip, k_quant.hip, k_ana_mw.hip, k_harm.hip, k_dec.hip, k_r24.hip,
+ * k_dsp_eval.hip, k_ana_eval.hip and k_par.hip, whose kernels read the
+ * constant tables, and k_state.hip and k_line.hip, whose kernels do not
+ * (k_link.hip needs none of it and includes only launch.h).
  *
  * Each TU is compiled separately (in parallel) into its own code object, so
- * each has its own copy of the constant tables (g_tab, g_der: tables.h) and
- * exports an upload function, MELPE_TU(name) -> melpe_tu_<name>_upload(),
- * that engine.hip calls once per device.  Kernels are launched through
+ * each TU whose kernels read the constant tables (g_tab, g_der: tables.h)
+ * has its own copy of them and exports an upload function, MELPE_TU(name) ->
+ * melpe_tu_<name>_upload(), that engine.hip calls once per device; a TU
+ * whose kernels read none has no MELPE_TU.  Kernels are launched through
  * extern "C" wrappers defined next to them (a kernel can only be launched
  * from its own TU without relocatable device code).  launch.h declares the
- * uploads and the wrappers, once, for both sides, and lists the TUs.
+ * uploads and the wrappers, once, for both sides, and lists the
+ * table-carrying TUs.
  *
  * Execution model: one lane per channel.  A kernel copies the
  * part of the channel's state it uses from its HBM record into the lane's

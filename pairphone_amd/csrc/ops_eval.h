@@ -1,6 +1,6 @@
 /*
  * ops_eval.h -- one basic operator of ops.h selected by id, for the device
- * basic-op parity test (engine.hip k_ops_eval, melpe_ops_eval_dev) and its
+ * basic-op parity test (k_dsp_eval.hip k_ops_eval, melpe_ops_eval_dev) and its
  * checker (oracle/ref_ops.c ref_ops_eval, which evaluates the reference's
  * own operators, melpe/mathhalf_i.h:120-2170 and melpe/mathdp31.c:71, with
  * the same ids and argument conventions).

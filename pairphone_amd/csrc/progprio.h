@@ -22,7 +22,7 @@
  * phase (7.47-7.51 vs 7.48-7.57 ms at 32,768 channels,
  * profiles/r06_t_mw_prio_ab.txt): its workgroup barriers already pace its
  * waves, so it has none.  The counter is
- * word 2 NBIN + 2 of the lane-order sort's control block (engine.hip
+ * word 2 NBIN + 2 of the lane-order sort's control block (launch.h
  * BinBuf, zeroed by k_bin_scan before each launch), so it needs the lane
  * order; MELPE_ANA_PRIO=0 / MELPE_DEC_PRIO=0 turn it off for A/Bs.
  * Priority changes only the order in which waves issue, never a value.

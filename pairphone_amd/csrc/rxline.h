@@ -22,7 +22,7 @@
  * fber and fau round as the reference's floats do: a double multiply rounded
  * to float, then a float add (link.h link_decay).
  *
- * Shared by the receive-loop kernel (engine.hip k_rx_line) and the
+ * Shared by the receive-loop kernel (k_line.hip k_rx_line) and the
  * host-emulation build.
  */
 #ifndef MELPE_RXLINE_H

@@ -12,7 +12,7 @@
  * and the reader tells them apart by bit 1 of the first byte
  * (melpe_dec.c:35).
  *
- * Shared by the stream kernels (engine.hip k_stream_*) and the host
+ * Shared by the stream kernels (k_line.hip k_stream_*) and the host
  * functions melpe_stream_pack / melpe_stream_unpack.
  */
 #ifndef MELPE_STREAM_FMT_H

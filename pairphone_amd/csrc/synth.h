@@ -25,7 +25,7 @@
 #define SYN_FN static inline
 #endif
 
-typedef struct {
+typedef struct synth_state {
 	uint32_t rng;		/* xorshift32 state, never 0 */
 	int32_t seg_left;	/* samples left in the current segment */
 	int32_t seg_type;	/* 0 voiced, 1 unvoiced, 2 silence */

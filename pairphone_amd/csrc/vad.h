@@ -13,7 +13,7 @@
  * not shared with ops.h.  Word16 = int16_t, Word32 = int32_t
  * (vad/typedefs.h:88-123 on this ABI).
  *
- * Shared by the GPU kernel (engine.hip) and the host-emulation build.
+ * Shared by the GPU kernel (k_line.hip k_vad) and the host-emulation build.
  */
 #ifndef MELPE_VAD_H
 #define MELPE_VAD_H

@@ -23,7 +23,7 @@
  *
  * Here the state is 25 64-bit lanes in registers and every round is fully
  * unrolled, so all lane indices and rotations are compile-time constants.
- * Shared by the GPU kernel (engine.hip) and the host-emulation build.
+ * Shared by the GPU kernel (k_line.hip k_voice_crypt) and the host-emulation build.
  */
 #ifndef MELPE_VOICE_CRYPT_H
 #define MELPE_VOICE_CRYPT_H

@@ -1,5 +1,5 @@
 """Device basic-op parity: the saturating operators as compiled for gfx950
-(ops.h through engine.hip k_ops_eval, melpe_ops_eval_dev) against the
+(ops.h through k_dsp_eval.hip k_ops_eval, melpe_ops_eval_dev) against the
 reference's own operators (melpe/mathhalf_i.h:120-2170, melpe/mathdp31.c:71,
 compiled by oracle/Makefile into oracle/_ref/libref_ops.so, ref_ops_eval).
 

@@ -8,7 +8,7 @@ branches.  This tool encodes N channels of the bench's input with the host
 build (emu_encode), reads each superframe's parameters (emu_enc_params) and
 cuts the channels into waves of 64 under two lane orders:
 
-  engine key   the first lane order (engine.hip bin_class): the voiced-frame
+  engine key   the first lane order (k_state.hip bin_class): the voiced-frame
                count and last pitch of the channel's PREVIOUS superframe;
   pattern key  the second lane order: uvc of the CURRENT superframe.
 
@@ -92,7 +92,7 @@ def wave_rows(p):
 
 
 def engine_key(prev_uvc, prev_pitch):
-    """engine.hip bin_class on the previous superframe"""
+    """k_state.hip bin_class on the previous superframe"""
     nv = 3 - ((prev_uvc >> 2) & 1) - ((prev_uvc >> 1) & 1) - (prev_uvc & 1)
     b = np.clip((prev_pitch >> 7) - 20, 0, 141)
     return nv * 142 + b
